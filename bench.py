@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- clips/s of OCPG's per-clip training step on MI355X (BASELINE.json config #2 / #3).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]         (N > 1: launched by torch.distributed.run)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]     (N > 1: launched by torch.distributed.run)
 
 One "step" = forward + criterion + backward + grad-clip + AdamW over `--clips-per-gpu` synthetic clips
 (5 x 3 x 384 x 640, ResNet-101 + 4-scale deformable transformer, 5 queries, bf16 autocast, fp32 MSDeformAttn /
 dynamic mask head as in the reference's --amp path).  Data-parallel over N GPUs (one process per GPU, DDP over
 RCCL), per-GPU work fixed => weak scaling.  Prints ONE JSON line on rank 0.
 
-Extra objects on that line:
+A plain run sets up, warms up, times the K steps and prints the line (headline figures only).  --dump-outputs DIR
+writes what the last timed step computed (rank 0: loss terms, model outputs, the gradient norm and a fixed sample of
+the gradients) as DIR/<name>.npy.  That step starts from the initial weights, put back in place before it, and the
+batch is seeded: its inputs are the same every run, so two builds can be compared output for output.
+
+Extra objects on that line, with --full only (each leg can still be dropped with its --no-* option):
   roofline     -- the hand-written kernel that dominates our HIP time (the grad_value scatter of the MSDeformAttn backward
                   at the encoder shape), timed live with events on the launch stream during the timed steps; achieved =
                   algorithmic bytes per launch / mean launch time, peak = 8 TB/s HBM.
@@ -16,6 +21,7 @@ Extra objects on that line:
                   microseconds from live events, fraction of the HBM / vector-FP32 peak), sorted by time per step.
   cpu_baseline -- the CPU oracle (oracle/ocpg_ref.py, a restatement of the reference's path; kind "port") timed on
                   this host for a bounded sample (one clip fwd+loss+bwd), rank 0, N=1 only.
+  b1           -- the same step at 1 clip per GPU (BASELINE config #2), graph launch mode, N=1 only.
 """
 import argparse
 import json
@@ -122,11 +128,12 @@ class EagerStep:
         self.__dict__.update(locals())
         self.scaler = torch.amp.GradScaler("cuda") if amp_dtype == torch.float16 else None
         self.grad_norm = None           # pre-clip total gradient norm of the last step (device scalar)
+        self.keep = None                # a dict: the last step's outputs are kept there (--dump-outputs)
 
     def __call__(self):
         self.optimizer.zero_grad(set_to_none=True)
         loss = forward_backward(self.ddp_model, self.criterion, self.make_samples(), self.text, self.targets, self.amp_dtype,
-                                scaler=self.scaler)
+                                keep=self.keep, scaler=self.scaler)
         if hasattr(self.optimizer, "step_clip"):
             if self.scaler is None:
                 self.grad_norm = self.optimizer.step_clip(self.args.clip_max_norm)     # norm + clip + AdamW: three launches
@@ -804,6 +811,52 @@ def choose_step(rungs, world, agree_device, reset, trial_steps=3, needs_finite=T
     return None, None
 
 
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: all files together
+DUMP_SAMPLE = 4 << 20            # elements kept of a larger array (a fixed, seeded sample of its flattened elements)
+
+
+def _dump_sample(t, seed):
+    """t flattened, or (more than DUMP_SAMPLE elements) the elements at sorted seeded indices: the same for every run of the same shape."""
+    t = t.detach().reshape(-1)
+    if t.numel() <= DUMP_SAMPLE:
+        return t
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).unique()
+    return t[idx.to(t.device)]
+
+
+def dump_outputs(path, step, model, loss):
+    """--dump-outputs: what the last timed step computed from the initial weights and the seeded batch, one DIR/<name>.npy each --
+    `loss` (the weighted total), every term of the criterion's loss dict under its own name, the model's prediction heads (`pred_*`),
+    the pre-clip gradient norm and a fixed sample of the gradients over the trainable parameters flattened in model order
+    (`grads_sample`).  Not the weights after the optimizer step: AdamW's moments carry the earlier steps, whose path differs from run
+    to run.  Floating tensors are written as float32 (float64 stays float64)."""
+    import numpy as np
+    kept = getattr(step, "static", None) or getattr(step, "keep", None) or {}
+    arrays = {"loss": loss}
+    for k, v in sorted(kept.get("loss_dict", {}).items()):
+        arrays[k] = torch.as_tensor(v)
+    for k, v in sorted(kept.get("out", {}).items()):
+        if k.startswith("pred_") and torch.is_tensor(v) and v.is_floating_point():
+            arrays[k] = v
+    if getattr(step, "grad_norm", None) is not None:
+        arrays["grad_norm"] = torch.as_tensor(step.grad_norm)
+    params = [p for p in model.parameters() if p.requires_grad]
+    arrays["grads_sample"] = _dump_sample(torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                                                     for p in params]), seed=0)
+    out = {}
+    for i, (k, v) in enumerate(arrays.items()):
+        v = _dump_sample(v, seed=1 + i) if v.numel() > DUMP_SAMPLE else v.detach()
+        out[k] = np.ascontiguousarray(v.to(torch.float64 if v.dtype == torch.float64 else torch.float32).cpu().numpy())
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return total
+
+
 def cpu_baseline(state_shapes):
     """Time the CPU oracle (a restatement of the reference path) on ONE clip: forward + criterion + backward."""
     try:
@@ -835,7 +888,14 @@ def main():
                          "replayed as ONE HIP graph (the eager step is host-bound: ~2 600 launches, 45 ms vs 40 ms); the graph is "
                          "checked against an eager step before the timed region and bench.py falls back to eager if that fails.")
     ap.add_argument("--graph", action="store_true", help="(default since round 2; kept for old command lines)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs after the timed steps: per-kernel timing (`roofline`, `kernels`), the B = 1 leg "
+                         "(`b1`) and the CPU oracle (`cpu_baseline`).  Default: the headline figures only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     a = ap.parse_args()
+    if not a.full:              # a plain run: set up, warm up, time the steps, print the line
+        a.no_kernel_timing = a.no_b1 = a.no_cpu_baseline = True
     T_FRAMES, HEIGHT, WIDTH = a.frames, a.height, a.width
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -882,6 +942,8 @@ def main():
         with torch.no_grad():
             for t in list(model.parameters()) + list(model.buffers()):
                 dist.broadcast(t, src=0)
+    # --dump-outputs: the initial weights, put back in place right before the last timed step (see the timed loop)
+    initial_weights = [p.detach().clone() for p in model.parameters()] if a.dump_outputs else None
     torch.manual_seed(42 + rank)    # per-rank stream for data and dropout only (main.py:44-45)
     optimizer = make_optimizer(model, args)
     amp_dtype = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": None}[a.dtype]
@@ -954,6 +1016,8 @@ def main():
         if world > 1:
             ddp_model = wrap_ddp(model, local_rank)
         step = EagerStep(model, ddp_model, criterion, optimizer, make_samples, text, targets, args, amp_dtype)
+        if a.dump_outputs:
+            step.keep = {}
 
     def sync():
         if world > 1:
@@ -967,7 +1031,13 @@ def main():
         msda_fn.enable_kernel_timing(True)          # 24 event pairs per step: no measurable host cost
     t0 = time.perf_counter()
     losses = []
-    for _ in range(a.steps):
+    for i in range(a.steps):
+        if initial_weights is not None and i == a.steps - 1:
+            # the steps before have trained the weights along a path that differs from run to run (atomic accumulations, GEMM
+            # kernels chosen by timing, both amplified by training from random init): the last step starts from the initial
+            # weights, so that what --dump-outputs writes is computed from the same inputs every run (one in-stream copy, no sync)
+            with torch.no_grad():
+                torch._foreach_copy_(list(model.parameters()), initial_weights)
         loss = step()
         losses.append(loss.clone())
     sync()
@@ -989,6 +1059,8 @@ def main():
         per_rank = [float(x.item()) for x in every]          # a straggler (a rank on slower kernels / a slower host) shows here
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = t.item()
+    if a.dump_outputs and rank == 0:        # before the --full legs: they run further steps on the same model
+        dump_outputs(a.dump_outputs, step, model, loss)
     kt = msda_fn.collect_kernel_timing() if (not a.no_kernel_timing and mode == "eager") else {}
     lib_kt, lib_steps, kt_steps = {}, 3, a.steps
     if not a.no_kernel_timing and rank == 0 and world == 1:

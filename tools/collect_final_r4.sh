@@ -12,7 +12,7 @@ for cold in 0 1; do
 done
 cat $O/msda_gv_paths.txt
 echo "[0] grad_value paths done"
-timeout -k 10 500 python3 bench.py > $O/bench_line_graph_2clips.json 2> $O/bench_graph.err || { tail -5 $O/bench_graph.err; exit 1; }
+timeout -k 10 500 python3 bench.py --full > $O/bench_line_graph_2clips.json 2> $O/bench_graph.err || { tail -5 $O/bench_graph.err; exit 1; }
 echo "[1] default bench done"; cut -c1-400 $O/bench_line_graph_2clips.json
 rm -rf /tmp/prof_main
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_main -- python3 bench.py --steps 6 --warmup 4 --no-cpu-baseline --no-kernel-timing --no-b1 > $O/bench_under_rocprof.log 2>&1 || exit 1

@@ -2,10 +2,10 @@
 # Steps [1]-[3] of tools/collect_profiles.sh (bench lines of the default command and its variants + rocprofv3 steady-state cut) as their own call.
 O=gpurun_out/collect; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-timeout -k 10 500 python bench.py > $O/bench_line_graph_2clips.json 2> $O/bench_graph.err || exit 1
+timeout -k 10 500 python bench.py --full > $O/bench_line_graph_2clips.json 2> $O/bench_graph.err || exit 1
 echo "[1] default bench done"
-timeout -k 10 300 python bench.py --eager --no-cpu-baseline > $O/bench_line_eager_2clips.json 2> $O/bench_eager.err || exit 1
-timeout -k 10 300 python bench.py --clips-per-gpu 1 --no-cpu-baseline > $O/bench_line_graph_1clip.json 2> $O/bench_1clip.err || exit 1
+timeout -k 10 300 python bench.py --full --eager --no-cpu-baseline > $O/bench_line_eager_2clips.json 2> $O/bench_eager.err || exit 1
+timeout -k 10 300 python bench.py --full --clips-per-gpu 1 --no-cpu-baseline > $O/bench_line_graph_1clip.json 2> $O/bench_1clip.err || exit 1
 OCPG_GRAPH_SEGMENTS=3 timeout -k 10 300 python bench.py --no-cpu-baseline --no-kernel-timing --no-b1 > $O/bench_line_graph_3segments.json 2> $O/bench_3seg.err || exit 1
 echo "[2] eager / 1-clip lines done"
 rm -rf /tmp/prof_main
