@@ -127,6 +127,21 @@ int ocpg_bn_act_fwd(const void* x, const float* scale, const float* shift, const
 int ocpg_bn_act_bwd(const void* gy, const void* y, const float* scale, void* gx, void* gskip,
                     long long n_outer, int C, long long inner, int relu, int dtype, void* stream);
 
+/* Input gradient of a 1x1 convolution (channels-last bf16) with the frozen-BN + ReLU backward of the layer in front in its epilogue
+ * (csrc/gemm_dgrad_bn.hip; MFMA, fp32 accumulation): replaces ocpg_gemm (input gradient) + ocpg_bn_act_bwd of the layer in front.
+ *   v[m,n] = sum_k a[m,k] w[k,n]         a [M,K] (the gradient after this convolution's BN backward), w [K = Cout][N = Cin] as it lies
+ *   v += c[m,n]                          c may be NULL; the block's parked identity-skip gradient
+ *   v  = mask[m,n] > 0 ? v : 0           mask may be NULL; the convolution's own input = that layer's post-ReLU output
+ *   out_skip[m,n] = bf16(v)              out_skip may be NULL, and may be c itself (in place)
+ *   out[m,n] = bf16(v * scale[n])        scale fp32 [N] or NULL (= 1)
+ * tile: 0 = 128 x 128, 1 = 64 x 128, 2 = 64 x 64 workgroup tiles; ocpg_gemm_dgrad_bn_tile returns the measured-best one (64 x 64) or -1
+ * (the shape is not served).  Deterministic; every tile gives the same bits.
+ * Declined (the caller keeps its GEMM + ocpg_bn_act_bwd): -2000 shape (N % tile width, K % 128), -2001 a pointer not 16-byte aligned,
+ * -2002 dtype other than 1 (bf16). */
+int ocpg_gemm_dgrad_bn_tile(long long M, int N, int K);
+int ocpg_gemm_dgrad_bn(const void* a, const void* w, const void* c, const void* mask, const float* scale, void* out, void* out_skip,
+                       long long M, int N, int K, int dtype, int tile, void* stream);
+
 /* Fused 3-D (shifted-)window attention of Video-Swin -- replaces WindowAttention3D.forward's score / bias / mask /
  * softmax / PV chain (models/video_swin_transformer.py:138-169) and the shift-mask tensor of compute_mask (:316-329).
  *   qkv    [BW, N, 3, H, head_dim]   output of the qkv Linear (BW = batch * windows), head_dim must be 32

@@ -1,7 +1,10 @@
 """1x1 convolution + frozen-BN affine (+ residual) (+ ReLU) of a channels-last map as ONE autograd node.
 
 Forward: ocpg_gemm (hipBLASLt, cached plan, straight on the NHWC buffers: no view ops) -> ocpg_bn_act_fwd in place.
-Backward: ocpg_bn_act_bwd -> input gradient GEMM + weight gradient GEMM (row-split, amp_cache.weight_grad's rule).
+Backward: ocpg_bn_act_bwd -> input gradient GEMM + weight gradient GEMM (row-split, amp_cache.weight_grad's rule).  Where x is the
+output of a conv + BN + ReLU node whose only consumer is this one (FUSED_DGRAD_BN), the input gradient is csrc/gemm_dgrad_bn.hip with that
+node's BN + ReLU backward in its epilogue, and that node skips its ocpg_bn_act_bwd; where y feeds such a node, this node's backward takes
+gz (and its skip gradient) from it instead of launching ocpg_bn_act_bwd.
 Replaces torchvision Bottleneck's conv1+bn1+relu, conv3+bn3(+identity)+relu and downsample conv+bn as the reference
 runs them (models/backbone.py:46-56 FrozenBatchNorm2d + nn.Conv2d).  The step is launch-bound on the host: one Python
 autograd node and 2 (forward) / 3-4 (backward) C calls replace two nodes and ~10 tensor-view ops per layer.
@@ -31,7 +34,13 @@ _SKIP_TOKENS = {}           # data_ptr of a conv1 input -> token; cleared at the
 # bn_act_bwd launch (33 launches, ~0.5 ms per step at config #2).  conv1's forward leaves a token under its output's address, conv2's
 # forward picks it up when its input IS that tensor.
 PREMASK = os.environ.get("OCPG_PREMASK_DGRAD", "1") != "0"
-_PREMASK_TOKENS = {}        # data_ptr of a conv1 + bn1 + ReLU output -> token; cleared with the skip tokens
+_PREMASK_TOKENS = {}        # data_ptr of a conv + BN + ReLU output -> token (_offer_token); cleared with the skip tokens
+# A/B switch: the same for the 1x1 input gradients (csrc/gemm_dgrad_bn.hip: an own MFMA GEMM whose epilogue hipBLASLt cannot express).
+# (a) conv3's input gradient applies conv2's frozen-BN + ReLU backward (gz2 = v * [y2 > 0] * scale2);  (b) an identity block's conv1 adds
+# the parked skip gradient and applies the previous block's conv3 BN + ReLU backward (m = (v + C) * [y > 0]: its skip gradient m and
+# gz = m * scale3).  The producer's backward then skips its ocpg_bn_act_bwd launch (57 of 63 per step at config #2).
+FUSED_DGRAD_BN = os.environ.get("OCPG_FUSED_DGRAD_BN", "1") != "0"
+_DGRAD_BN_DECLINED = (-2000, -2001, -2002)      # ocpg_gemm_dgrad_bn: shape / alignment / dtype it does not serve (the caller keeps its path)
 
 
 def reset_skip_tokens():
@@ -48,6 +57,56 @@ def _same_tensor(a, b):
 
 def _tensor_key(t):
     return (t.data_ptr(), tuple(t.shape), t.dtype, tuple(t.stride()), t._version)
+
+
+def _offer_token(y, scale, skip, switch):
+    """Producer's forward: y = relu(bn(...)) may have its frozen-BN + ReLU backward done by the input-gradient kernel of the consumer whose
+    input IS y.  (The token identifies y by value, not by reference: ctx -> token -> y -> grad_fn -> ctx would be a cycle that keeps this
+    forward's autograd graph alive until the garbage collector runs -- and a stale graph inside a later stream capture is the
+    hipStreamEndCapture crash of DESIGN.md section 5.)"""
+    tok = {"y": _tensor_key(y), "scale": scale, "skip": skip, "switch": switch, "gz": None, "gskip": None, "ver": None}
+    _PREMASK_TOKENS[y.data_ptr()] = tok
+    return tok
+
+
+def _claim_token(x):
+    """Consumer's forward: the producer's token when x IS its output (else None)."""
+    tok = _PREMASK_TOKENS.pop(x.data_ptr(), None)
+    return tok if (tok is not None and tok["y"] == _tensor_key(x)) else None
+
+
+def _fill_token(tok, gz, gskip=None):
+    """Consumer's backward: gz (and the skip gradient) of the producer, written by the fused input-gradient kernel."""
+    tok["gz"], tok["gskip"], tok["ver"] = gz, gskip, gz._version
+
+
+def _take_token(tok, gy):
+    """Producer's backward: (gz, gskip) when the consumer already applied this layer's BN + ReLU backward, else None (ocpg_bn_act_bwd).
+    A fused gradient must arrive as it was written: any other tensor (a second consumer's gradient added to it, a hook) would be
+    masked and scaled a second time, so that is an error, never a fall-through."""
+    if tok is None or tok["gz"] is None:
+        return None
+    gz, gskip, ver = tok["gz"], tok["gskip"], tok["ver"]
+    tok["gz"] = tok["gskip"] = tok["ver"] = None
+    if not (gy.data_ptr() == gz.data_ptr() and gy.shape == gz.shape and gy.stride() == gz.stride() and gy._version == ver):
+        raise RuntimeError(f"{tok['switch']}=1: the gradient of this conv + BN + ReLU output was produced with the BN + ReLU backward already "
+                           f"applied by its consumer's input-gradient kernel, but a different gradient arrived (a second consumer of the "
+                           f"output, or a gradient hook); run with {tok['switch']}=0 for such a graph")
+    return gz, gskip
+
+
+def _dgrad_bn(a, w, c, mask, scale, out, out_skip, m, n, k, st):
+    """out [m, n] (+ out_skip) = the input gradient a w with the producer's BN + ReLU backward (csrc/gemm_dgrad_bn.hip); returns the status
+    (0, or one of _DGRAD_BN_DECLINED: nothing written)."""
+    L = lib()
+    tile = int(L.ocpg_gemm_dgrad_bn_tile(m, n, k))
+    if tile < 0:
+        return _DGRAD_BN_DECLINED[0]
+    rc = L.ocpg_gemm_dgrad_bn(a.data_ptr(), w.data_ptr(), None if c is None else c.data_ptr(), mask.data_ptr(), scale.data_ptr(), out.data_ptr(),
+                              None if out_skip is None else out_skip.data_ptr(), m, n, k, _DT.get(a.dtype, -1), tile, st)
+    if rc and rc not in _DGRAD_BN_DECLINED:
+        check(rc, "ocpg_gemm_dgrad_bn")
+    return rc
 
 
 def _reduce_partials(part, w_is_cast_copy):
@@ -123,13 +182,13 @@ class Conv1x1BNAct(Function):
         ctx.meta = (bool(relu), skip is not None, splits)
         ctx.w_cast = is_cast_copy(w)
         ctx.give = ctx.take = None
-        ctx.premask = None
+        # consumer: x IS a conv + BN + ReLU output whose BN + ReLU backward this node's input-gradient kernel can take over
+        ctx.claim = _claim_token(x) if (FUSED_DGRAD_BN and x.dtype == torch.bfloat16 and ctx.needs_input_grad[0]) else None
+        ctx.premask = None          # producer: the token of y
         if PREMASK and relu and skip is None and x.dtype == torch.bfloat16 and ctx.needs_input_grad[1]:
-            # (the token identifies y by value, not by reference: ctx -> token -> y -> grad_fn -> ctx would be a cycle that keeps this
-            # forward's autograd graph alive until the garbage collector runs -- and a stale graph inside a later stream capture is the
-            # hipStreamEndCapture crash of DESIGN.md section 5)
-            ctx.premask = {"y": _tensor_key(y), "scale": scale, "gz": None}
-            _PREMASK_TOKENS[y.data_ptr()] = ctx.premask
+            ctx.premask = _offer_token(y, scale, False, "OCPG_PREMASK_DGRAD")
+        elif FUSED_DGRAD_BN and relu and skip is not None and x.dtype == torch.bfloat16 and any(ctx.needs_input_grad):
+            ctx.premask = _offer_token(y, scale, True, "OCPG_FUSED_DGRAD_BN")
         if SKIP_GRAD_IN_GEMM:
             if skip is not None:
                 tok = _SKIP_TOKENS.pop(skip.data_ptr(), None)
@@ -154,10 +213,11 @@ class Conv1x1BNAct(Function):
         if gy.dtype != y.dtype or not gy.is_contiguous(memory_format=_CL):
             gy = gy.to(y.dtype).contiguous(memory_format=_CL)
         need_x, need_w, need_skip = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_skip and ctx.needs_input_grad[4]
-        tok = ctx.premask
-        if tok is not None and tok["gz"] is not None and tok["gz"].data_ptr() == gy.data_ptr() and tok["gz"].shape == gy.shape:
-            gz, gskip = gy, None            # the consumer's input-gradient kernel already applied this layer's frozen-BN + ReLU backward
-            tok["gz"] = None
+        fused = _take_token(ctx.premask, gy)
+        if fused is not None:               # the consumer's input-gradient kernel already applied this layer's frozen-BN + ReLU backward
+            gz, gskip = fused
+            if not need_skip:
+                gskip = None
         else:
             gz = torch.empty_like(y)
             gskip = torch.empty_like(y) if need_skip else None
@@ -174,13 +234,25 @@ class Conv1x1BNAct(Function):
             parked, ctx.take["g"], ctx.take["x"] = ctx.take["g"], None, None
         if need_x:      # gx[m, c] = gz[m, co] w[co, c] (+ the block's skip gradient, accumulated in place)
             acc = parked is not None and parked.dtype == x.dtype and parked.shape == x.shape and parked.is_contiguous(memory_format=_CL)
-            gx = parked if acc else torch.empty((n, c, h, wd), dtype=x.dtype, device=x.device, memory_format=_CL)
-            rc = L.ocpg_gemm(gz.data_ptr(), w.data_ptr(), gx.data_ptr(), None, dt, dt, 0, 0, m, c, co, co, c, c, 1, 0, 0, 0, 1.0,
-                             1.0 if acc else 0.0, st)
-            if rc:
-                check(rc, "ocpg_gemm")
-            if parked is not None and not acc:
-                gx = gx + parked
+            tok = ctx.claim
+            gx = None
+            # the producer of x without a skip input (site a) needs gz only; with one (site b: the previous block's conv3) the kernel also
+            # writes its skip gradient, which is complete only when it adds this block's parked identity-skip gradient
+            if tok is not None and (parked is None or acc) and (acc or not tok["skip"]):
+                gx = torch.empty((n, c, h, wd), dtype=x.dtype, device=x.device, memory_format=_CL)
+                out_skip = parked if tok["skip"] else None          # in place over the parked gradient (C), same element, same thread
+                if _dgrad_bn(gz, w, parked if acc else None, x, tok["scale"], gx, out_skip, m, c, co, st) == 0:
+                    _fill_token(tok, gx, out_skip)
+                else:
+                    gx = None
+            if gx is None:
+                gx = parked if acc else torch.empty((n, c, h, wd), dtype=x.dtype, device=x.device, memory_format=_CL)
+                rc = L.ocpg_gemm(gz.data_ptr(), w.data_ptr(), gx.data_ptr(), None, dt, dt, 0, 0, m, c, co, co, c, c, 1, 0, 0, 0, 1.0,
+                                 1.0 if acc else 0.0, st)
+                if rc:
+                    check(rc, "ocpg_gemm")
+                if parked is not None and not acc:
+                    gx = gx + parked
         elif parked is not None:
             gx = parked
         if need_w:      # gw[co, c] = gz[m, co]^T x[m, c], rows split into `splits` chunks (one strided-batched GEMM + a sum)
@@ -340,8 +412,11 @@ class Conv3x3MfmaBNAct(Function):
         from ...amp_cache import is_cast_copy
         ctx.meta = (bool(relu), splits, stride)
         ctx.w_cast = is_cast_copy(w)
-        tok = _PREMASK_TOKENS.pop(x.data_ptr(), None) if PREMASK else None
-        ctx.premask = tok if (tok is not None and tok["y"] == _tensor_key(x) and ctx.needs_input_grad[0]) else None
+        tok = _claim_token(x) if PREMASK else None
+        ctx.premask = tok if (tok is not None and not tok["skip"] and ctx.needs_input_grad[0]) else None
+        # producer (site a): y's one consumer, the bottleneck's conv3, may apply this BN + ReLU backward in its input-gradient kernel
+        ctx.offer = (_offer_token(y, scale, False, "OCPG_FUSED_DGRAD_BN")
+                     if (FUSED_DGRAD_BN and relu and x.dtype == torch.bfloat16 and any(ctx.needs_input_grad)) else None)
         return y
 
     @staticmethod
@@ -356,8 +431,12 @@ class Conv3x3MfmaBNAct(Function):
         st = torch.cuda.current_stream().cuda_stream
         if gy.dtype != y.dtype or not gy.is_contiguous(memory_format=_CL):
             gy = gy.to(y.dtype).contiguous(memory_format=_CL)
-        gz = torch.empty_like(y)
-        check(L.ocpg_bn_act_bwd(gy.data_ptr(), y.data_ptr(), scale.data_ptr(), gz.data_ptr(), None, m, co, 1, int(relu), 1, st), "ocpg_bn_act_bwd")
+        fused = _take_token(ctx.offer, gy)
+        if fused is not None:       # conv3's input-gradient kernel already applied this layer's frozen-BN + ReLU backward
+            gz = gy
+        else:
+            gz = torch.empty_like(y)
+            check(L.ocpg_bn_act_bwd(gy.data_ptr(), y.data_ptr(), scale.data_ptr(), gz.data_ptr(), None, m, co, 1, int(relu), 1, st), "ocpg_bn_act_bwd")
         gx = gw = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty((n, c, h, wd), dtype=y.dtype, device=y.device, memory_format=_CL)
@@ -376,7 +455,7 @@ class Conv3x3MfmaBNAct(Function):
                 check(L.ocpg_conv3x3_mfma_dgrad_masked(gz.data_ptr(), wt.data_ptr(), mask_ptr, scale_ptr, n, h, wd, c, co, stride, gx.data_ptr(), st),
                       "ocpg_conv3x3_mfma_dgrad_masked")
             if tok is not None:
-                tok["gz"] = gx
+                _fill_token(tok, gx)
         if ctx.needs_input_grad[1]:
             from ...amp_cache import side_wgrad
             with side_wgrad(ctx.w_cast, gz, x) as sw:          # off the critical path: the weight-gradient stream (amp_cache.side_wgrad)
