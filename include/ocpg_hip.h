@@ -114,6 +114,48 @@ int ocpg_msda_bwd_f64(const double* value, const int64_t* shapes, const int64_t*
                       int N, int S, int M, int D, int L, int Lq, int P,
                       double* grad_value, double* grad_loc, double* grad_attn, void* stream);
 
+/* MSDeformAttn with 16-BIT STORAGE of value / out / grad_out (opt-in; the reference's op is fp32 / fp64 only, so these entry points
+ * have no counterpart there and the parity statement does not cover them).
+ *   dtype: 1 = bfloat16, 2 = float16 (the numbering of ocpg_bn_act_*: 0 would be float32 -- use the _f32 entry points); any other
+ *          value returns an invalid-argument status and launches nothing.
+ *   value [N, S, M, D], out / grad_out [N, Lq, M*D]: 16-bit elements of `dtype`.
+ *   loc, attn, grad_loc, grad_attn: float32 (a normalised coordinate on an 80-wide map does not survive 8 mantissa bits).
+ *   grad_value [N, S, M, D]: float32, ACCUMULATED into (caller zeroes it), exactly as ocpg_msda_bwd_f32 -- there are no 16-bit atomics.
+ *   Arithmetic is fp32 throughout; every 16-bit element is widened exactly at its load and `out` is rounded to nearest-even once, at
+ *   its store.  With value' = value widened to fp32 (exact), _fwd_h16 returns round(ocpg_msda_fwd_f32(value')) up to fp32 summation
+ *   order, and _bwd_h16 the gradients ocpg_msda_bwd_f32(value', grad_out') gives, up to fp32 summation order.
+ *   Any D is served; D % 4 == 0 (D / 4 a power of two <= 64) takes the fast row kernels when value / out / grad_out are 16-byte
+ *   aligned -- the alignment is examined before anything is launched and a buffer that misses it takes the generic kernels (the
+ *   self-attention route of _bwd_h16 also wants loc / attn / grad_value on 16 bytes, as its output-tiled kernels do; otherwise the row
+ *   kernel with the atomic scatter serves the call).  The fast forward and gather use 8 channels (16 bytes) per lane, or 4 where the
+ *   per-row sample records of 8 would not fit the LDS; results do not depend on it beyond fp32 summation order.
+ *   _bwd_h16 is the WHOLE backward for any shape.  shapes_host (may be NULL) and sel_state (may be NULL) as for ocpg_msda_bwd_f32 /
+ *   ocpg_msda_bwd_value_sel_f32: with a host copy of the shapes, Lq == S and D in {16, 32} grad_value comes from the column-scatter /
+ *   output-tiled kernels (which read grad_out in 16 bits) under the call site's path selection, grad_loc / grad_attn from the gather
+ *   row kernel.  Forced paths: OCPG_MSDA_TILE / OCPG_MSDA_COL as documented above; the legacy column variants behind
+ *   OCPG_MSDA_COL_LP = 1..3 read fp32 only, so with one of them forced the whole 16-bit backward takes the generic kernel.
+ *   shapes_host of _fwd_h16 is accepted for symmetry and not read.
+ *   The fused front end (ocpg_msda_fused_*_f32) has no 16-bit form: a 16-bit caller keeps the unfused path. */
+int ocpg_msda_fwd_h16(const void* value, const int64_t* shapes, const int64_t* level_start,
+                      const float* loc, const float* attn,
+                      int N, int S, int M, int D, int L, int Lq, int P,
+                      void* out, const int64_t* shapes_host, int dtype, void* stream);
+int ocpg_msda_bwd_h16(const void* value, const int64_t* shapes, const int64_t* level_start,
+                      const float* loc, const float* attn, const void* grad_out,
+                      int N, int S, int M, int D, int L, int Lq, int P,
+                      float* grad_value, float* grad_loc, float* grad_attn,
+                      const int64_t* shapes_host, int* sel_state, int dtype, void* stream);
+/* The two halves of _bwd_h16 for the self-attention shape on their own, as ocpg_msda_bwd_value_sel_f32 / ocpg_msda_bwd_locattn_f32 (a
+ * caller that wants only some gradients, or the two kernels timed apart).  -2000: shape, alignment or forced path not served, nothing
+ * launched -- call ocpg_msda_bwd_h16 then. */
+int ocpg_msda_bwd_value_h16(const float* loc, const float* attn, const void* grad_out,
+                            int N, int S, int M, int D, int L, int Lq, int P,
+                            float* grad_value, const int64_t* shapes_host, int* sel_state, int dtype, void* stream);
+int ocpg_msda_bwd_locattn_h16(const void* value, const int64_t* shapes, const int64_t* level_start,
+                              const float* loc, const float* attn, const void* grad_out,
+                              int N, int S, int M, int D, int L, int Lq, int P,
+                              float* grad_loc, float* grad_attn, int dtype, void* stream);
+
 /* Fused frozen-BatchNorm affine (+ residual) (+ ReLU) over a feature map -- replaces the per-BN elementwise chain of
  * FrozenBatchNorm2d.forward (models/backbone.py:46-56: x*scale + bias with scale = w*rsqrt(var+1e-5)) followed by
  * torchvision Bottleneck's "out += identity" / ReLU.  scale/shift are the per-channel fp32 vectors [C].

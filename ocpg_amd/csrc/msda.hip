@@ -29,43 +29,16 @@
 #include "msda_col.h"
 #include "msda_tile.h"
 #include "msda_dev.h"
+#include "msda_host.h"
 
 namespace {
 
 constexpr int kMaxLevels = 16;
 
-// One precomputed sample, 32 bytes = two ds_read_b128.
-struct __attribute__((aligned(16))) SampleRec {
-  int off00;      // element offset (in scalars, relative to value[b, 0, m, 0]) of corner (y0, x0); may be "virtual" (negative) when that corner is outside
-  int rowstride;  // W * M * D
-  int mask;       // bit k set <=> corner k (0:(y0,x0) 1:(y0,x1) 2:(y1,x0) 3:(y1,x1)) is inside the map; 0 => sample skipped
-  float a;        // attention weight
-  float ly, lx;   // fractional parts
-  float H, W;     // level size as float (grad_loc scaling)
-};
-
-template <typename T>
-__device__ __forceinline__ void make_sample(T x_n, T y_n, T a, int H, int W, int lstart, int MD, SampleRec& r) {
-  const T h_im = y_n * (T)H - (T)0.5;
-  const T w_im = x_n * (T)W - (T)0.5;
-  r.a = (float)a;
-  r.H = (float)H;
-  r.W = (float)W;
-  r.rowstride = W * MD;
-  if (h_im > (T)-1 && w_im > (T)-1 && h_im < (T)H && w_im < (T)W) {
-    const int y0 = (int)floor(h_im), x0 = (int)floor(w_im);
-    r.ly = (float)(h_im - (T)y0);
-    r.lx = (float)(w_im - (T)x0);
-    const bool y0ok = y0 >= 0, y1ok = y0 + 1 <= H - 1, x0ok = x0 >= 0, x1ok = x0 + 1 <= W - 1;
-    r.mask = (y0ok && x0ok ? 1 : 0) | (y0ok && x1ok ? 2 : 0) | (y1ok && x0ok ? 4 : 0) | (y1ok && x1ok ? 8 : 0);
-    r.off00 = (lstart + y0 * W + x0) * MD;
-  } else {
-    r.ly = r.lx = 0.f;
-    r.mask = 0;
-    r.off00 = 0;
-  }
-}
-
+using ocpg_dev::SampleRec;
+using ocpg_dev::make_sample;
+using ocpg_dev::GatherRec;
+using ocpg_dev::make_gather;
 using ocpg_dev::ld4;
 using ocpg_dev::group_sum;
 using ocpg_dev::reduce_scatter_g8_p4;
@@ -265,12 +238,6 @@ __global__ __launch_bounds__(256) void msda_fwd_generic(const T* __restrict__ va
 //   * validity is folded into the per-axis weights (hy' = y0 >= 0 ? 1-ly : 0 ...) and the corner addresses are clamped
 //     into the map, so the inner loop has no masks and no selects: 4 unconditional 16-B loads, packed FMAs;
 //   * 4 samples are reduced together by a DPP reduce-scatter (12 moves) instead of 9 LDS-crossbar shuffles per sample.
-struct __attribute__((aligned(16))) GatherRec {
-  int pk;          // element offset of corner (ya, xa) relative to value[b, 0, m, 0]  |  iy1<<3 | iy0<<2 | ix1<<1 | ix0
-  int rowstride;   // W * M * D
-  float aW, aH;    // attention weight * level width / height (grad_loc scaling)
-  float hy, ly, hx, lx;   // masked by validity
-};
 
 // FUSED (round 4; G = 8, L*P = 16): the epilogue applies the backward of the module's softmax and writes the gradient of the merged query
 // projection [N*Lq, 3*M*NS] = [d offsets | d logits] (gloc = that matrix, gattn unused) instead of grad_loc / grad_attn -- ATen's
@@ -304,26 +271,8 @@ __global__ __launch_bounds__(256) void msda_bwd_gather_row(const float* __restri
     const float* arow = attn + row * NS;
     for (int s = j; s < NS; s += G) {
       const int l = s / P;
-      const int H = lvlH[l], W = lvlW[l];
       GatherRec rec;
-      const float h_im = lrow[2 * s + 1] * (float)H - 0.5f, w_im = lrow[2 * s] * (float)W - 0.5f;
-      const float a = arow[s];
-      rec.rowstride = W * MD;
-      if (h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W) {
-        const int y0 = (int)floorf(h_im), x0 = (int)floorf(w_im);
-        const float ly = h_im - (float)y0, lx = w_im - (float)x0;
-        const bool iy0 = y0 >= 0, iy1 = y0 + 1 <= H - 1, ix0 = x0 >= 0, ix1 = x0 + 1 <= W - 1;
-        rec.hy = iy0 ? 1.f - ly : 0.f;
-        rec.ly = iy1 ? ly : 0.f;
-        rec.hx = ix0 ? 1.f - lx : 0.f;
-        rec.lx = ix1 ? lx : 0.f;
-        rec.aW = a * (float)W;
-        rec.aH = a * (float)H;
-        rec.pk = ((lvlS[l] + max(y0, 0) * W + max(x0, 0)) * MD) | (iy1 ? 8 : 0) | (iy0 ? 4 : 0) | (ix1 ? 2 : 0) | (ix0 ? 1 : 0);
-      } else {
-        rec.hy = rec.ly = rec.hx = rec.lx = rec.aW = rec.aH = 0.f;
-        rec.pk = 0;
-      }
+      make_gather(lrow[2 * s], lrow[2 * s + 1], arow[s], lvlH[l], lvlW[l], lvlS[l], MD, rec);
       recs[r * NS + s] = rec;
     }
   }
@@ -978,20 +927,21 @@ inline int launch_status() {
 
 // ---- the two halves of the self-attention backward (also exported on their own: include/ocpg_hip.h) -----------------
 // 1 = launched, 0 = shape not served by these kernels
-inline int launch_bwd_value_col(const float* loc, const float* attn, const float* grad_out, const int64_t* shapes_host, int N, int S,
-                                int M, int D, int L, int Lq, int P, float* grad_value, hipStream_t st) {
+// go_dtype: storage of grad_out (0 = float32, 1 = bfloat16, 2 = float16: the _h16 entry points of msda_h16.hip)
+inline int launch_bwd_value_col(const float* loc, const float* attn, const void* grad_out, const int64_t* shapes_host, int N, int S,
+                                int M, int D, int L, int Lq, int P, float* grad_value, hipStream_t st, int go_dtype = 0) {
   const int G = fast_group(D);
   if (!(shapes_host && Lq == S && col_enabled() && (G == 4 || G == 8) && (long long)S * M * D < (1LL << 31))) return 0;
   // round 3: output-tiled kernels (plain stores for the fine levels, no halo re-flush: csrc/msda_tile.hip).  Measured at config #2,
   // N = 10 (tools/bench_msda_gv.py, profiles/r03_msda_gv_paths.json): 261-280 us against the column scatter's 213 us on the model's
   // INITIAL ring offsets, 334-364 against 502 us on perturbed ("trained") offsets -- opt-in (OCPG_MSDA_TILE=1) until it wins both.
   const char* te = std::getenv("OCPG_MSDA_TILE");
-  if (te && te[0] == '1' && ocpg_tile::bwd_value_tile(loc, attn, grad_out, shapes_host, N, S, M, D, L, P, grad_value, st)) return 1;
+  if (te && te[0] == '1' && ocpg_tile::bwd_value_tile(loc, attn, grad_out, shapes_host, N, S, M, D, L, P, grad_value, st, nullptr, 0, go_dtype)) return 1;
   ocpg_col::ColGeom cg;
   const char* tw = std::getenv("OCPG_MSDA_TILEW");      // experiment switch: scatter tile width on the finest level
   static const int mlo = [] { const char* e = std::getenv("OCPG_MSDA_MARGIN_LO"); return e ? std::atoi(e) : ocpg_col::kScatterMarginLo; }();    // A/B
   if (!ocpg_col::make_col_geom(shapes_host, L, S, M, P, 8, tw ? std::atoi(tw) : 16, cg, mlo, ocpg_col::kMarginHi)) return 0;
-  return ocpg_col::bwd_scatter_col(loc, attn, grad_out, N, S, M, D, P, cg, grad_value, st);
+  return ocpg_col::bwd_scatter_col(loc, attn, grad_out, N, S, M, D, P, cg, grad_value, st, nullptr, 0, go_dtype);
 }
 
 inline int launch_bwd_locattn_row(const float* value, const int64_t* shapes, const int64_t* level_start, const float* loc,
@@ -1010,6 +960,34 @@ inline int launch_bwd_locattn_row(const float* value, const int64_t* shapes, con
 }
 
 }  // namespace
+
+// grad_value of the self-attention shape for every grad_out storage type (msda_host.h): the body of ocpg_msda_bwd_value_sel_f32.
+// 0 = launched, -2000 = shape / forced path not served (nothing launched), -2001 / -2002 = a family refused after the geometry checks.
+int ocpg_msda::bwd_value_sel(const float* loc, const float* attn, const void* grad_out, int go_dtype, int N, int S, int M, int D, int L,
+                             int Lq, int P, float* grad_value, const int64_t* shapes_host, int* sel_state, hipStream_t st) {
+  const bool forced = std::getenv("OCPG_MSDA_TILE") != nullptr || !col_enabled();
+  if (sel_state && !forced && shapes_host && Lq == S && D == 32 && (long long)S * M * D < (1LL << 31)) {
+    // thresholds (percent of far samples as the ACTIVE family counts them), measured at config #2, N = 10 (tools/bench_msda_gv.py, GV_SELECT=1):
+    //   offsets                      column: far share, us      tiled: far share, us
+    //   initial ring                      0.0 %   169                0.0 %   279
+    //   ring + N(0, 1.5 px) + 2 % far     3.0 %   241                3.6 %   305
+    //   ring + N(0, 3 px) + 5 % far       9.3 %   432               12.5 %   361
+    static const int to_tile = [] { const char* e = std::getenv("OCPG_MSDA_SEL_TO_TILE"); return e ? std::atoi(e) : 6; }();
+    static const int to_col = [] { const char* e = std::getenv("OCPG_MSDA_SEL_TO_COL"); return e ? std::atoi(e) : 6; }();
+    static const int mlo = [] { const char* e = std::getenv("OCPG_MSDA_MARGIN_LO"); return e ? std::atoi(e) : ocpg_col::kScatterMarginLo; }();
+    ocpg_col::ColGeom cg;
+    if (ocpg_col::make_col_geom(shapes_host, L, S, M, P, 8, 16, cg, mlo, ocpg_col::kMarginHi) && ocpg_col::select_supported(cg, D, P) &&
+        ocpg_tile::tile_supported(shapes_host, N, L, S, M, P, D)) {
+      if (ocpg_col::bwd_scatter_col(loc, attn, grad_out, N, S, M, D, P, cg, grad_value, st, sel_state, to_tile, go_dtype) != 2) return -2001;
+      if (!ocpg_tile::bwd_value_tile(loc, attn, grad_out, shapes_host, N, S, M, D, L, P, grad_value, st, sel_state, to_col, go_dtype)) return -2002;
+      ocpg_col::select_commit(sel_state, to_tile, to_col, st);
+      return 0;
+    }
+  }
+  if (!launch_bwd_value_col(loc, attn, grad_out, shapes_host, N, S, M, D, L, Lq, P, grad_value, st, go_dtype)) return -2000;
+  return 0;
+}
+
 
 #define FAST_DISPATCH(G_, KERNEL, ...)                                                          \
   switch (G_) {                                                                                 \
@@ -1176,27 +1154,7 @@ int ocpg_msda_bwd_value_sel_f32(const float* loc, const float* attn, const float
   if (!attn) return -1002;
   if (!grad_out) return -1003;
   if (!grad_value) return -1011;
-  hipStream_t st = (hipStream_t)stream;
-  const bool forced = std::getenv("OCPG_MSDA_TILE") != nullptr || !col_enabled();
-  if (sel_state && !forced && shapes_host && Lq == S && D == 32 && (long long)S * M * D < (1LL << 31)) {
-    // thresholds (percent of far samples as the ACTIVE family counts them), measured at config #2, N = 10 (tools/bench_msda_gv.py, GV_SELECT=1):
-    //   offsets                      column: far share, us      tiled: far share, us
-    //   initial ring                      0.0 %   169                0.0 %   279
-    //   ring + N(0, 1.5 px) + 2 % far     3.0 %   241                3.6 %   305
-    //   ring + N(0, 3 px) + 5 % far       9.3 %   432               12.5 %   361
-    static const int to_tile = [] { const char* e = std::getenv("OCPG_MSDA_SEL_TO_TILE"); return e ? std::atoi(e) : 6; }();
-    static const int to_col = [] { const char* e = std::getenv("OCPG_MSDA_SEL_TO_COL"); return e ? std::atoi(e) : 6; }();
-    static const int mlo = [] { const char* e = std::getenv("OCPG_MSDA_MARGIN_LO"); return e ? std::atoi(e) : ocpg_col::kScatterMarginLo; }();
-    ocpg_col::ColGeom cg;
-    if (ocpg_col::make_col_geom(shapes_host, L, S, M, P, 8, 16, cg, mlo, ocpg_col::kMarginHi) && ocpg_col::select_supported(cg, D, P) &&
-        ocpg_tile::tile_supported(shapes_host, N, L, S, M, P, D)) {
-      if (ocpg_col::bwd_scatter_col(loc, attn, grad_out, N, S, M, D, P, cg, grad_value, st, sel_state, to_tile) != 2) return -2001;
-      if (!ocpg_tile::bwd_value_tile(loc, attn, grad_out, shapes_host, N, S, M, D, L, P, grad_value, st, sel_state, to_col)) return -2002;
-      ocpg_col::select_commit(sel_state, to_tile, to_col, st);
-      return launch_status();
-    }
-  }
-  if (!launch_bwd_value_col(loc, attn, grad_out, shapes_host, N, S, M, D, L, Lq, P, grad_value, st)) return -2000;
+  if (int e = ocpg_msda::bwd_value_sel(loc, attn, grad_out, 0, N, S, M, D, L, Lq, P, grad_value, shapes_host, sel_state, (hipStream_t)stream)) return e;
   return launch_status();
 }
 

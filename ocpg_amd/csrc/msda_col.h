@@ -64,7 +64,8 @@ bool select_supported(const ColGeom& g, int D, int P);
 // Each returns 1 (2: the launched kernel honours `sel`) when it launched, 0 when the shape is not supported (nothing launched).
 int fwd_col(const float* value, const float* loc, const float* attn, int N, int S, int M, int D, int P, const ColGeom& g,
             float* out, hipStream_t st);
-int bwd_scatter_col(const float* loc, const float* attn, const float* gout, int N, int S, int M, int D, int P, const ColGeom& g,
-                    float* gvalue, hipStream_t st, int* sel = nullptr, int to_tile_pct = 0);
+// go_dtype: storage of gout (0 = float32, 1 = bfloat16, 2 = float16); the 16-bit forms are served by the default one-pass kernel only
+int bwd_scatter_col(const float* loc, const float* attn, const void* gout, int N, int S, int M, int D, int P, const ColGeom& g,
+                    float* gvalue, hipStream_t st, int* sel = nullptr, int to_tile_pct = 0, int go_dtype = 0);
 
 }  // namespace ocpg_col

@@ -1200,9 +1200,10 @@ __device__ __forceinline__ void pair_flush(const float4& acc, int gpix, int odd,
   }
 }
 
-template <int NT>
+// GT: storage type of grad_out (float, or the 16-bit tags of msda_dev.h for the _h16 entry points; converted at the one load site)
+template <int NT, typename GT = float>
 __global__ __launch_bounds__(NT, 6) void k_scatter_col4(const float* __restrict__ loc, const float* __restrict__ attn,
-                                                         const float* __restrict__ gout, int S, int M, ColGeom geo,
+                                                         const GT* __restrict__ gout, int S, int M, ColGeom geo,
                                                          float* __restrict__ gvalue, int* __restrict__ sel, int to_tile_pct) {
   // path selection (msda_col.h): this kernel is path 0; when the call site's state says the output-tiled kernels serve this call, every
   // workgroup leaves at once
@@ -1701,8 +1702,26 @@ bool select_supported(const ColGeom& g, int D, int P) {
   return (!e || std::atoi(e) >= 4) && scatter4_ok(g, D, P);
 }
 
-int bwd_scatter_col(const float* loc, const float* attn, const float* gout, int N, int S, int M, int D, int P, const ColGeom& g,
-                    float* gvalue, hipStream_t st, int* sel, int to_tile_pct) {
+template <typename GT>
+static int launch_scatter_col4(const float* loc, const float* attn, const GT* gout, int N, int S, int M, const ColGeom& g, float* gvalue,
+                               hipStream_t st, int* sel, int to_tile_pct) {
+  const size_t lds4 = scatter4_lds(g);
+  if (lds4 > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_scatter_col4<768, GT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
+  k_scatter_col4<768, GT><<<(unsigned)((long long)N * g.ntiles * M), 768, lds4, st>>>(loc, attn, gout, S, M, g, gvalue, sel, to_tile_pct);
+  return 2;
+}
+
+int bwd_scatter_col(const float* loc, const float* attn, const void* gout_, int N, int S, int M, int D, int P, const ColGeom& g,
+                    float* gvalue, hipStream_t st, int* sel, int to_tile_pct, int go_dtype) {
+  if (go_dtype != 0) {      // 16-bit grad_out: the default (one-pass, patch-owned) kernel only; the legacy variants below stay fp32
+    const char* e = std::getenv("OCPG_MSDA_COL_LP");
+    if ((e && std::atoi(e) < 4) || !scatter4_ok(g, D, P)) return 0;
+    if (go_dtype == 1) return launch_scatter_col4(loc, attn, static_cast<const ocpg_dev::bf16s*>(gout_), N, S, M, g, gvalue, st, sel, to_tile_pct);
+    if (go_dtype == 2) return launch_scatter_col4(loc, attn, static_cast<const ocpg_dev::fp16s*>(gout_), N, S, M, g, gvalue, st, sel, to_tile_pct);
+    return 0;
+  }
+  const float* gout = static_cast<const float*>(gout_);
   {
     const char* e = std::getenv("OCPG_MSDA_COL_LP");      // A/B (read per call: tests toggle it): 4 = one pass, patch-owned sums (default), 3 = one pass, pixel-owned sums, 2 = level pairs, 1 = one level per pass
     const int lp = e ? std::atoi(e) : 4;

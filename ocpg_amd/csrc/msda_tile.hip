@@ -31,6 +31,7 @@
 namespace ocpg_tile {
 namespace {
 
+using ocpg_dev::ld1;
 using ocpg_dev::ld4;
 
 constexpr int NT = 256, G = 8, D = 32, NGRP = NT / G;     // 32 lane groups of 8 lanes: a group owns pixels, a lane 4 channels
@@ -207,8 +208,10 @@ struct TileSh {
   unsigned short list[kListMax];          // (query | level << 15) of every candidate with at least one corner inside the footprint
 };
 
+// GT: storage type of grad_out (float, or the 16-bit tags of msda_dev.h; converted at the one load site)
+template <typename GT = float>
 __global__ __launch_bounds__(NT, 4) void k_gv_tile(const float* __restrict__ loc, const float* __restrict__ attn,
-                                                const float* __restrict__ gout, int S, int M, TileTab tab, float* __restrict__ gvalue,
+                                                const GT* __restrict__ gout, int S, int M, TileTab tab, float* __restrict__ gvalue,
                                                 const int* __restrict__ sel) {
   if (sel != nullptr && sel[ocpg_col::kSelCur] != 1) return;      // path selection: the column scatter serves this call
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -362,9 +365,9 @@ struct CoarseSh {
   int cnt[NGRP * NPX], start[NGRP * NPX];
 };
 
-template <int NPX>
+template <int NPX, typename GT = float>
 __global__ __launch_bounds__(NT, NPX <= 10 ? 3 : 1) void k_gv_coarse(const float* __restrict__ loc, const float* __restrict__ attn,
-                                                  const float* __restrict__ gout, int S, int M, TileTab tab, float* __restrict__ gvalue,
+                                                  const GT* __restrict__ gout, int S, int M, TileTab tab, float* __restrict__ gvalue,
                                                   int* __restrict__ sel, int to_col_pct) {
   // path selection: runs only when the call site's state says so; it then also proposes the next call's path (stay while the share of
   // far samples stays above to_col_pct)
@@ -409,8 +412,8 @@ __global__ __launch_bounds__(NT, NPX <= 10 ? 3 : 1) void k_gv_coarse(const float
 #pragma unroll
       for (int u = 0; u < NB / NGRP; ++u) {
         const int qi = min(bi + nbatch * (grp + u * NGRP), nq - 1);
-        const float* g = gout + ((rowb + kq + (long long)K * qi) * M + m) * D + j;
-        gq[u] = make_float4(g[0], g[G], g[2 * G], g[3 * G]);
+        const GT* g = gout + ((rowb + kq + (long long)K * qi) * M + m) * D + j;
+        gq[u] = make_float4(ld1(g), ld1(g + G), ld1(g + 2 * G), ld1(g + 3 * G));
       }
 #pragma unroll
       for (int u = 0; u < NB / NGRP; ++u) *reinterpret_cast<float4*>(gs + (grp + u * NGRP) * D + 4 * j) = gq[u];
@@ -650,27 +653,36 @@ bool tile_supported(const int64_t* shapes_host, int N, int L, int S, int M, int 
   return make_tile_tab(shapes_host, N, L, S, M, P, Dm, tab);
 }
 
-int bwd_value_tile(const float* loc, const float* attn, const float* gout, const int64_t* shapes_host, int N, int S, int M, int Dm, int L,
-                   int P, float* gvalue, hipStream_t st, int* sel, int to_col_pct) {
+template <typename GT>
+static int launch_value_tile(const float* loc, const float* attn, const GT* gout, const TileTab& tab, int N, int S, int M, float* gvalue,
+                             hipStream_t st, int* sel, int to_col_pct) {
+  const size_t ldsA = sizeof(Item) * kItems + sizeof(float) * NB * D + sizeof(TileSh);
+  allow_lds(k_gv_tile<GT>, ldsA);
+  k_gv_tile<GT><<<(unsigned)((long long)N * tab.ntiles * M), NT, ldsA, st>>>(loc, attn, gout, S, M, tab, gvalue, sel);
+  const unsigned gridB = (unsigned)((long long)N * tab.K * M);
+  if (tab.nbB <= NGRP * 10) {
+    const size_t ldsB = sizeof(Item) * kItems + sizeof(float) * NB * D + sizeof(CoarseSh<10>);
+    allow_lds(k_gv_coarse<10, GT>, ldsB);
+    k_gv_coarse<10, GT><<<gridB, NT, ldsB, st>>>(loc, attn, gout, S, M, tab, gvalue, sel, to_col_pct);
+  } else {
+    const size_t ldsB = sizeof(Item) * kItems + sizeof(float) * NB * D + sizeof(CoarseSh<20>);
+    allow_lds(k_gv_coarse<20, GT>, ldsB);
+    k_gv_coarse<20, GT><<<gridB, NT, ldsB, st>>>(loc, attn, gout, S, M, tab, gvalue, sel, to_col_pct);
+  }
+  return 1;
+}
+
+int bwd_value_tile(const float* loc, const float* attn, const void* gout, const int64_t* shapes_host, int N, int S, int M, int Dm, int L,
+                   int P, float* gvalue, hipStream_t st, int* sel, int to_col_pct, int go_dtype) {
   static_assert(sizeof(TileTab) <= 3600, "TileTab travels as a kernel argument (4 KB limit with the other arguments)");
   TileTab tab;
   if (!make_tile_tab(shapes_host, N, L, S, M, P, Dm, tab)) return 0;
   if ((reinterpret_cast<uintptr_t>(loc) | reinterpret_cast<uintptr_t>(attn) | reinterpret_cast<uintptr_t>(gout) |
        reinterpret_cast<uintptr_t>(gvalue)) & 15) return 0;
-  const size_t ldsA = sizeof(Item) * kItems + sizeof(float) * NB * D + sizeof(TileSh);
-  allow_lds(k_gv_tile, ldsA);
-  k_gv_tile<<<(unsigned)((long long)N * tab.ntiles * M), NT, ldsA, st>>>(loc, attn, gout, S, M, tab, gvalue, sel);
-  const unsigned gridB = (unsigned)((long long)N * tab.K * M);
-  if (tab.nbB <= NGRP * 10) {
-    const size_t ldsB = sizeof(Item) * kItems + sizeof(float) * NB * D + sizeof(CoarseSh<10>);
-    allow_lds(k_gv_coarse<10>, ldsB);
-    k_gv_coarse<10><<<gridB, NT, ldsB, st>>>(loc, attn, gout, S, M, tab, gvalue, sel, to_col_pct);
-  } else {
-    const size_t ldsB = sizeof(Item) * kItems + sizeof(float) * NB * D + sizeof(CoarseSh<20>);
-    allow_lds(k_gv_coarse<20>, ldsB);
-    k_gv_coarse<20><<<gridB, NT, ldsB, st>>>(loc, attn, gout, S, M, tab, gvalue, sel, to_col_pct);
-  }
-  return 1;
+  if (go_dtype == 1) return launch_value_tile(loc, attn, static_cast<const ocpg_dev::bf16s*>(gout), tab, N, S, M, gvalue, st, sel, to_col_pct);
+  if (go_dtype == 2) return launch_value_tile(loc, attn, static_cast<const ocpg_dev::fp16s*>(gout), tab, N, S, M, gvalue, st, sel, to_col_pct);
+  if (go_dtype != 0) return 0;
+  return launch_value_tile(loc, attn, static_cast<const float*>(gout), tab, N, S, M, gvalue, st, sel, to_col_pct);
 }
 
 }  // namespace ocpg_tile

@@ -20,6 +20,7 @@ from . import amp_cache
 from .attention import MultiheadAttention
 from .ops.functions import fused_ln_func
 from .ops.modules import MSDeformAttn
+from .ops.modules.ms_deform_attn import resolve_value_dtype
 
 FUSED_GLUE = True       # A/B switch: fused dropout+add+LayerNorm and bias+ReLU+dropout kernels (csrc/fused_ln.hip)
 
@@ -86,9 +87,11 @@ class DeformableTransformerEncoderLayer(nn.Module):
         self.norm2 = nn.LayerNorm(d_model)
 
     def forward(self, src, pos, reference_points, spatial_shapes, level_start_index, padding_mask=None):
+        vd = self.self_attn.active_value_dtype(src)          # 16-bit value path (opt-in): no up-cast of src for it; the query path stays fp32
         with torch.autocast(device_type=src.device.type, enabled=False):
             q = src.float() if pos is None else src.float() + pos.float()
-            attn = self.self_attn(q, reference_points, src.float(), spatial_shapes, level_start_index, padding_mask)[0]
+            attn = self.self_attn(q, reference_points, src.float() if vd is None else src, spatial_shapes, level_start_index, padding_mask,
+                                  value_dtype=vd)[0]
         src = _drop_add_norm(attn, src, self.dropout1, self.norm1)
         ffn = self.linear2(_ffn_hidden(src, self.linear1, self.activation, self.dropout2))
         return _drop_add_norm(ffn, src, self.dropout3, self.norm2)
@@ -147,9 +150,11 @@ class DeformableTransformerDecoderLayer(nn.Module):
         qk = tgt if query_pos is None else tgt + query_pos
         sa = self.self_attn(qk.transpose(0, 1), qk.transpose(0, 1), tgt.transpose(0, 1)).transpose(0, 1)
         tgt = _drop_add_norm(sa, tgt, self.dropout2, self.norm2)
+        vd = self.cross_attn.active_value_dtype(src)
         with torch.autocast(device_type=tgt.device.type, enabled=False):
             q = tgt.float() if query_pos is None else tgt.float() + query_pos.float()
-            ca, loc, weights = self.cross_attn(q, reference_points, src.float(), src_spatial_shapes, level_start_index, src_padding_mask)
+            ca, loc, weights = self.cross_attn(q, reference_points, src.float() if vd is None else src, src_spatial_shapes, level_start_index,
+                                               src_padding_mask, value_dtype=vd)
         tgt = _drop_add_norm(ca, tgt, self.dropout1, self.norm1)
         ffn = self.linear2(_ffn_hidden(tgt, self.linear1, self.activation, self.dropout3))
         return _drop_add_norm(ffn, tgt, self.dropout4, self.norm3), loc, weights
@@ -234,7 +239,7 @@ class _LevelPos(torch.autograd.Function):
 class DeformableTransformer(nn.Module):
     def __init__(self, d_model=256, nhead=8, num_encoder_layers=6, num_decoder_layers=6, dim_feedforward=1024,
                  dropout=0.1, activation="relu", return_intermediate_dec=False, num_feature_levels=4,
-                 dec_n_points=4, enc_n_points=4, two_stage=False, two_stage_num_proposals=300):
+                 dec_n_points=4, enc_n_points=4, two_stage=False, two_stage_num_proposals=300, msda_value_dtype=None):
         super().__init__()
         assert not two_stage, "args.two_stage must be false!"   # ocpg.py:65
         self.d_model, self.nhead, self.dropout = d_model, nhead, dropout
@@ -248,6 +253,9 @@ class DeformableTransformer(nn.Module):
             num_decoder_layers, return_intermediate_dec)
         self.level_embed = nn.Parameter(torch.empty(num_feature_levels, d_model))
         self.reference_points = amp_cache.Linear(d_model, 2)
+        for m in self.modules():
+            if isinstance(m, MSDeformAttn):
+                m.set_value_dtype(msda_value_dtype)         # None: the reference's fp32 island (ops/modules/ms_deform_attn.py)
         self._reset_parameters()
 
     def _reset_parameters(self):
@@ -326,9 +334,12 @@ class DeformableTransformer(nn.Module):
 
 
 def build_deforamble_transformer(args):
+    # public switch of the opt-in 16-bit MSDeformAttn value path: the field when it is not None (absent on reference-side Namespaces),
+    # else OCPG_MSDA_VALUE_DTYPE, else fp32; an unknown word raises here, at build time
+    vd = resolve_value_dtype(getattr(args, "msda_value_dtype", None))
     return DeformableTransformer(
         d_model=args.hidden_dim, nhead=args.nheads, num_encoder_layers=args.enc_layers,
         num_decoder_layers=args.dec_layers, dim_feedforward=args.dim_feedforward, dropout=args.dropout,
         activation="relu", return_intermediate_dec=True, num_feature_levels=args.num_feature_levels,
         dec_n_points=args.dec_n_points, enc_n_points=args.enc_n_points, two_stage=args.two_stage,
-        two_stage_num_proposals=args.num_queries)
+        two_stage_num_proposals=args.num_queries, msda_value_dtype=vd)

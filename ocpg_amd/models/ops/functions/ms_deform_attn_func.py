@@ -67,12 +67,34 @@ def _dims(value, loc):
     return N, S, M, D, L, Lq, P
 
 
+# 16-bit STORAGE of value / out / grad_out (include/ocpg_hip.h: ocpg_msda_*_h16): the C ABI's dtype codes
+_H16 = {torch.bfloat16: 1, torch.float16: 2}
+
+
+def _check_h16(fn, value, sampling_loc, attn_weight):
+    """a 16-bit value needs fp32 sampling locations and attention weights (coordinates do not survive 8 mantissa bits)"""
+    for n, t in (("sampling_loc", sampling_loc), ("attn_weight", attn_weight)):
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{fn}: with a {value.dtype} value, {n} must be float32 (got {t.dtype})")
+
+
 def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step=64):
     for n, t in (("value", value), ("spatial_shapes", spatial_shapes), ("level_start_index", level_start_index),
                  ("sampling_loc", sampling_loc), ("attn_weight", attn_weight)):
         require_gpu(n, t)
+    if value.dtype in _H16:
+        _check_h16("ms_deform_attn_forward", value, sampling_loc, attn_weight)
+        if spatial_shapes.dtype != torch.int64 or level_start_index.dtype != torch.int64:
+            raise RuntimeError("ms_deform_attn_forward: spatial_shapes / level_start_index must be int64")
+        N, S, M, D, L, Lq, P = _dims(value, sampling_loc)
+        out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
+        with torch.cuda.device(value.device), _timed("fwd_enc" if Lq == S else "fwd_dec"):
+            check(lib().ocpg_msda_fwd_h16(value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
+                                          sampling_loc.data_ptr(), attn_weight.data_ptr(), N, S, M, D, L, Lq, P, out.data_ptr(),
+                                          None, _H16[value.dtype], stream_ptr()), "ocpg_msda_fwd_h16")
+        return out
     if value.dtype not in (torch.float32, torch.float64):
-        raise RuntimeError("ms_deform_attn_forward: only float32 / float64 are supported")
+        raise RuntimeError("ms_deform_attn_forward: only float32 / float64 (and bfloat16 / float16 storage of value) are supported")
     if sampling_loc.dtype != value.dtype or attn_weight.dtype != value.dtype:
         raise RuntimeError("ms_deform_attn_forward: value / sampling_loc / attn_weight dtypes differ")
     if spatial_shapes.dtype != torch.int64 or level_start_index.dtype != torch.int64:
@@ -101,6 +123,23 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
                  ("sampling_loc", sampling_loc), ("attn_weight", attn_weight), ("grad_output", grad_output)):
         require_gpu(n, t)
     N, S, M, D, L, Lq, P = _dims(value, sampling_loc)
+    if value.dtype in _H16:
+        # whole backward behind one entry point; grad_value is accumulated in fp32 (no 16-bit atomics) and handed back in value's dtype
+        _check_h16("ms_deform_attn_backward", value, sampling_loc, attn_weight)
+        if grad_output.dtype != value.dtype:
+            raise RuntimeError(f"ms_deform_attn_backward: grad_output must have value's dtype {value.dtype} (got {grad_output.dtype})")
+        grad_value = torch.zeros(value.shape, dtype=torch.float32, device=value.device)
+        grad_loc = torch.empty_like(sampling_loc)
+        grad_attn = torch.empty_like(attn_weight)
+        hs = _host_shapes(spatial_shapes) if Lq == S else None
+        with torch.cuda.device(value.device), _timed("bwd_enc" if Lq == S else "bwd_dec"):
+            check(lib().ocpg_msda_bwd_h16(value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
+                                          sampling_loc.data_ptr(), attn_weight.data_ptr(), grad_output.data_ptr(),
+                                          N, S, M, D, L, Lq, P, grad_value.data_ptr(), grad_loc.data_ptr(), grad_attn.data_ptr(),
+                                          ctypes.c_void_p(hs.data_ptr()) if hs is not None else None,
+                                          sel_state.data_ptr() if sel_state is not None else None, _H16[value.dtype], stream_ptr()),
+                  "ocpg_msda_bwd_h16")
+        return grad_value.to(value.dtype), grad_loc, grad_attn
     grad_value = torch.zeros_like(value)
     grad_loc = torch.empty_like(sampling_loc)
     grad_attn = torch.empty_like(attn_weight)
@@ -140,7 +179,7 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
                                           N, S, M, D, L, Lq, P, grad_value.data_ptr(), grad_loc.data_ptr(),
                                           grad_attn.data_ptr(), stream_ptr()), "ocpg_msda_bwd")
         else:
-            raise RuntimeError("ms_deform_attn_backward: only float32 / float64 are supported")
+            raise RuntimeError("ms_deform_attn_backward: only float32 / float64 (and bfloat16 / float16 storage of value) are supported")
     return grad_value, grad_loc, grad_attn
 
 
@@ -170,6 +209,7 @@ class MSDeformAttnFusedFunction(Function):
     and `reference + offset` (ms_deform_attn.py:96-110, 2-d reference branch) inside the forward kernel's sample setup, the softmax backward
     and the [d offsets | d logits] layout inside the gather kernel's epilogue.  Self-attention calls only (Lq == S), D = 32, L*P = 16,
     reference points without gradient; `supported()` says whether a call qualifies -- the module keeps the unfused path otherwise.
+    fp32 only: the fused kernels have no 16-bit-storage form, so a bfloat16 / float16 value is not supported here and takes the unfused op.
 
     apply(value [N,S,M,D], shapes, level_start, qproj [N,Lq,3*M*L*P], ref [N,Lq,L,2], L, P, sel_state) -> (out, loc, attn)"""
 

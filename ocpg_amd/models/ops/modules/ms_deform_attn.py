@@ -2,7 +2,8 @@
 
 Same parameters, initialisation and forward contract as the reference's
 models/ops/modules/ms_deform_attn.py:31-118 (returns (output, sampling_locations, attention_weights)).
-Runs in fp32 regardless of autocast, as the reference does (deformable_transformer.py:250,329).
+Runs in fp32 regardless of autocast, as the reference does (deformable_transformer.py:250,329) -- unless the caller opts into
+16-bit storage of the value path (`value_dtype`; a deviation from the reference, see `resolve_value_dtype`).
 """
 import math
 import os
@@ -12,6 +13,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from ... import amp_cache
 from ...amp_cache import TokenLinear, linear
 from ....util.misc import memo
 from ..functions import MSDeformAttnFunction
@@ -23,6 +25,22 @@ SELECT_PATH = os.environ.get("OCPG_MSDA_SELECT", "1") != "0"     # A/B switch: p
 MERGED_QUERY_PROJ = True      # A/B switch: sampling_offsets and attention_weights as ONE GEMM over the query (they share their input)
 
 
+_UNSET = object()
+_VALUE_DTYPES = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16, "autocast": "autocast"}
+
+
+def resolve_value_dtype(word=None):
+    """The module's `value_dtype` for the public switch (args.msda_value_dtype / OCPG_MSDA_VALUE_DTYPE): the argument when it is not
+    None, else the environment variable, else "fp32".  -> None (fp32 island, the reference's behaviour), torch.bfloat16, torch.float16,
+    or "autocast" (follow torch.get_autocast_dtype("cuda") while autocast is on, fp32 otherwise).  An unknown word raises ValueError."""
+    src = "msda_value_dtype"
+    if word is None:
+        word, src = os.environ.get("OCPG_MSDA_VALUE_DTYPE") or "fp32", "OCPG_MSDA_VALUE_DTYPE"
+    if word not in _VALUE_DTYPES:
+        raise ValueError(f"{src} must be one of {sorted(_VALUE_DTYPES)}, not {word!r}")
+    return _VALUE_DTYPES[word]
+
+
 def _is_power_of_2(n):
     if not isinstance(n, int) or n < 0:
         raise ValueError(f"invalid input for _is_power_of_2: {n} (type: {type(n)})")
@@ -30,7 +48,11 @@ def _is_power_of_2(n):
 
 
 class MSDeformAttn(nn.Module):
-    def __init__(self, d_model=256, n_levels=4, n_heads=8, n_points=4):
+    def __init__(self, d_model=256, n_levels=4, n_heads=8, n_points=4, value_dtype=None):
+        """value_dtype: None = the reference's fp32 island.  torch.bfloat16 / torch.float16 (or "autocast": the autocast dtype while
+        autocast is on) = 16-bit STORAGE of the value path on the GPU: value_proj, the padding fill, the op's value / output and
+        output_proj run in that dtype (fp32 accumulation inside the kernels); the query projections, the softmax, the location arithmetic
+        and the returned sampling_locations / attention_weights stay fp32.  Opt-in: not what the reference computes."""
         super().__init__()
         if d_model % n_heads:
             raise ValueError(f"d_model must be divisible by n_heads, but got {d_model} and {n_heads}")
@@ -45,7 +67,37 @@ class MSDeformAttn(nn.Module):
         # path-selection state of this module's backward (include/ocpg_hip.h: ocpg_msda_bwd_value_sel_f32): which grad_value kernel family the
         # next call takes, kept on the device by the kernels themselves.  Not part of the state_dict (checkpoints stay interchangeable).
         self.register_buffer("_sel_state", torch.zeros(8, dtype=torch.int32), persistent=False)
+        self.set_value_dtype(value_dtype)
         self._reset_parameters()
+
+    def set_value_dtype(self, value_dtype):
+        """A CONSTRUCTION-TIME setting (the model builder calls it before the first forward): the owning model caches its fused-cast
+        parameter list at its first autocast forward (amp_cache._param_groups), so a change after that would leave value_proj /
+        output_proj out of (or stale in) the one-launch cast and the 16-bit path would pay a weight cast per call."""
+        if value_dtype not in (None, torch.bfloat16, torch.float16, "autocast"):
+            raise ValueError(f"value_dtype must be None, torch.bfloat16, torch.float16 or 'autocast', not {value_dtype!r}")
+        self.value_dtype = value_dtype
+        if value_dtype is not None:
+            # the two value-path projections join the model's one-launch parameter cast (amp_cache.scope): no per-call weight cast
+            amp_cache.register(self, self.value_proj.weight, self.value_proj.bias, self.output_proj.weight, self.output_proj.bias)
+        else:
+            self.__dict__.pop("_amp_cache_extra", None)
+
+    def active_value_dtype(self, x):
+        """The 16-bit dtype this call's value path runs in, or None (fp32).  Callers that wrap the module in autocast(enabled=False)
+        ask BEFORE they do ("autocast" reads the ambient autocast state) and hand the answer to forward(value_dtype=...)."""
+        vd = self.value_dtype
+        if vd is None or not x.is_cuda:
+            return None
+        if vd == "autocast":
+            vd = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else None
+            return vd if vd in (torch.bfloat16, torch.float16) else None
+        return vd
+
+    @staticmethod
+    def _linear16(x, lin, dt):
+        w, b = amp_cache.lookup(lin.weight), amp_cache.lookup(lin.bias)
+        return linear(x.to(dt), w.to(dt), b.to(dt))          # (.to is the identity for this forward's working copies under matching autocast)
 
     def _reset_parameters(self):
         """Zero offset/attention weights; offset bias = 8-direction ring scaled by the point index (ms_deform_attn.py:64-78)."""
@@ -65,8 +117,11 @@ class MSDeformAttn(nn.Module):
         nn.init.zeros_(self.output_proj.bias)
 
     def forward(self, query, reference_points, input_flatten, input_spatial_shapes, input_level_start_index,
-                input_padding_mask=None):
+                input_padding_mask=None, value_dtype=_UNSET):
+        """value_dtype: what a caller that wraps the module in autocast(enabled=False) got from active_value_dtype() (None = fp32);
+        left out, the module asks itself."""
         N, Lq, _ = query.shape
+        vd = self.active_value_dtype(input_flatten) if value_dtype is _UNSET else value_dtype
         _, S, _ = input_flatten.shape
         M, L, P = self.n_heads, self.n_levels, self.n_points
         host = getattr(input_spatial_shapes, "_ocpg_host", None)
@@ -75,7 +130,7 @@ class MSDeformAttn(nn.Module):
         else:
             assert (input_spatial_shapes[:, 0] * input_spatial_shapes[:, 1]).sum() == S
 
-        value = self.value_proj(input_flatten)
+        value = self.value_proj(input_flatten) if vd is None else self._linear16(input_flatten, self.value_proj, vd)
         if input_padding_mask is not None:
             value = value.masked_fill(input_padding_mask[..., None], 0.0)
         value = value.view(N, S, M, self.d_model // M)
@@ -93,6 +148,7 @@ class MSDeformAttn(nn.Module):
                            .expand(M, L, P, 2).reshape(-1).to(query.device))
                 so_w, so_b = so_w * inv[:, None], so_b * inv
             both = linear(query, torch.cat([so_w, self.attention_weights.weight], 0), torch.cat([so_b, self.attention_weights.bias], 0))
+            # (a 16-bit value is not `supported`: the fused kernels are fp32 only, the un-fused op below has the 16-bit form)
             if (FUSED_FRONT and folded and Lq == S and MSDeformAttnFusedFunction.supported(value, both, reference_points, L, P)):
                 # lines 96-110 of the reference module inside the kernels: no softmax / add / split-cat passes over the [N, Lq, 384] projection
                 out, loc, weights = MSDeformAttnFusedFunction.apply(value.contiguous(), input_spatial_shapes, input_level_start_index, both,
@@ -120,4 +176,4 @@ class MSDeformAttn(nn.Module):
             loc_c._ocpg_sel = self._sel_state
         out = MSDeformAttnFunction.apply(value.contiguous(), input_spatial_shapes, input_level_start_index,
                                          loc_c, weights.contiguous(), self.im2col_step)
-        return self.output_proj(out), loc, weights
+        return (self.output_proj(out) if vd is None else self._linear16(out, self.output_proj, vd)), loc, weights

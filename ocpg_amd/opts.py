@@ -20,7 +20,10 @@ def default_args(**over):
         set_cost_class=2, set_cost_bbox=5, set_cost_giou=2, set_cost_mask=2, set_cost_boundary=2, set_cost_dice=5,
         mask_loss_coef=2, boundary_loss_coef=2, dice_loss_coef=5, proj_loss_coef=5, lst_loss_coef=2, cls_loss_coef=2,
         bbox_loss_coef=5, giou_loss_coef=2, eos_coef=0.1, focal_alpha=0.25, eval=False, seed=42,
-        text_encoder_lazy=True)
+        text_encoder_lazy=True,
+        # storage dtype of MSDeformAttn's value / out: None | "fp32" | "bf16" | "fp16" | "autocast" (opt-in 16-bit mode, a deviation from
+        # the reference's fp32 op; None = the environment variable OCPG_MSDA_VALUE_DTYPE, else "fp32": models/ops/modules/ms_deform_attn.py)
+        msda_value_dtype=None)
     for k, v in over.items():
         setattr(ns, k, v)
     return ns
