@@ -135,7 +135,7 @@ int ocpg_msda_bwd_f64(const double* value, const int64_t* shapes, const int64_t*
  *   row kernel.  Forced paths: OCPG_MSDA_TILE / OCPG_MSDA_COL as documented above; the legacy column variants behind
  *   OCPG_MSDA_COL_LP = 1..3 read fp32 only, so with one of them forced the whole 16-bit backward takes the generic kernel.
  *   shapes_host of _fwd_h16 is accepted for symmetry and not read.
- *   The fused front end (ocpg_msda_fused_*_f32) has no 16-bit form: a 16-bit caller keeps the unfused path. */
+ *   The fused front end has a 16-bit form of its own: ocpg_msda_fused_fwd_h16 / ocpg_msda_fused_bwd_qproj_h16 below. */
 int ocpg_msda_fwd_h16(const void* value, const int64_t* shapes, const int64_t* level_start,
                       const float* loc, const float* attn,
                       int N, int S, int M, int D, int L, int Lq, int P,
@@ -155,6 +155,24 @@ int ocpg_msda_bwd_locattn_h16(const void* value, const int64_t* shapes, const in
                               const float* loc, const float* attn, const void* grad_out,
                               int N, int S, int M, int D, int L, int Lq, int P,
                               float* grad_loc, float* grad_attn, int dtype, void* stream);
+/* FUSED FRONT END with 16-bit storage: ocpg_msda_fused_fwd_f32 / ocpg_msda_fused_bwd_qproj_f32 (above) for a 16-bit value / out / grad_out.
+ *   qproj, ref, loc_out, attn_out, loc, attn, grad_qproj: float32, laid out as for the _f32 symbols; value, out, grad_out: 16-bit
+ *   elements of `dtype` (1 = bfloat16, 2 = float16; any other value returns an invalid-argument status and launches nothing).
+ *   _fwd:       softmax over the 16 logits and `reference + offset` in fp32 in the row's sample set-up, loc_out / attn_out written in
+ *               fp32, then the sampling of ocpg_msda_fwd_h16 (fp32 accumulation, `out` rounded to nearest-even once at its store).
+ *   _bwd_qproj: the gather of ocpg_msda_bwd_locattn_h16 with the softmax backward in its epilogue; writes grad_qproj and nothing else
+ *               (no atomics: bit-reproducible).  grad_value keeps coming from ocpg_msda_bwd_value_h16 with the call site's sel_state.
+ *   Lane mapping as for the un-fused 16-bit kernels: 8 channels per lane by default, OCPG_MSDA_H16_LANES=4 forces 4.
+ *   -2000 (nothing launched, every pointer examined first): D != 32, L*P != 16, value / out / grad_out off a 16-byte boundary, or
+ *   qproj / ref / loc_out / grad_qproj off an 8-byte boundary.  The caller keeps ocpg_msda_fwd_h16 / ocpg_msda_bwd_h16 then. */
+int ocpg_msda_fused_fwd_h16(const void* value, const int64_t* shapes, const int64_t* level_start,
+                            const float* qproj, const float* ref,
+                            int N, int S, int M, int D, int L, int Lq, int P,
+                            void* out, float* loc_out, float* attn_out, int dtype, void* stream);
+int ocpg_msda_fused_bwd_qproj_h16(const void* value, const int64_t* shapes, const int64_t* level_start,
+                                  const float* loc, const float* attn, const void* grad_out,
+                                  int N, int S, int M, int D, int L, int Lq, int P,
+                                  float* grad_qproj, int dtype, void* stream);
 
 /* Fused frozen-BatchNorm affine (+ residual) (+ ReLU) over a feature map -- replaces the per-BN elementwise chain of
  * FrozenBatchNorm2d.forward (models/backbone.py:46-56: x*scale + bias with scale = w*rsqrt(var+1e-5)) followed by

@@ -31,6 +31,8 @@ SIGNATURES = {
     "ocpg_msda_bwd_h16": [_vp, _i64p, _i64p, _vp, _vp, _vp] + [_int] * 7 + [_vp, _vp, _vp, _vp, _vp, _int, _vp],
     "ocpg_msda_bwd_value_h16": [_vp, _vp, _vp] + [_int] * 7 + [_vp, _vp, _vp, _int, _vp],
     "ocpg_msda_bwd_locattn_h16": [_vp, _i64p, _i64p, _vp, _vp, _vp] + [_int] * 7 + [_vp, _vp, _int, _vp],
+    "ocpg_msda_fused_fwd_h16": [_vp, _i64p, _i64p, _vp, _vp] + [_int] * 7 + [_vp, _vp, _vp, _int, _vp],
+    "ocpg_msda_fused_bwd_qproj_h16": [_vp, _i64p, _i64p, _vp, _vp, _vp] + [_int] * 7 + [_vp, _int, _vp],
     "ocpg_bn_act_fwd": [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _int, ctypes.c_longlong, _int, _int, _vp],
     "ocpg_bn_act_bwd": [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _int, ctypes.c_longlong, _int, _int, _vp],
     "ocpg_gemm_dgrad_bn_tile": [ctypes.c_longlong, _int, _int],

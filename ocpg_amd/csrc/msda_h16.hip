@@ -9,7 +9,8 @@
 //   CPL = 4: the fp32 kernels' lane structure (G = D / 4, DPP reduce-scatter over 8 lanes unchanged), 8-byte corner loads;
 //   CPL = 8: 16-byte corner loads as in fp32 (G = D / 8: for D = 32 four lanes per row, 16 rows per wave), half the load
 //            instructions per sample; the gather's sums over the row's lanes then stay inside a DPP quad.
-// Both exist for the forward and the gather; OCPG_MSDA_H16_LANES=4|8 forces one (A/B timing: tools/bench_msda_h16.py), the defaults
+// Both exist for the forward and the gather, un-fused and with the module's front end fused in (msda_fwd_fused_h16 /
+// msda_bwd_gather_fused_h16: D = 32, L * P = 16); OCPG_MSDA_H16_LANES=4|8 forces one (A/B timing: tools/bench_msda_h16.py), the defaults
 // below are what DESIGN.md section 4.3b records.
 //
 // The grad_value half of the self-attention backward reuses the column-scatter / output-tiled kernels (msda_col.hip, msda_tile.hip),
@@ -417,6 +418,228 @@ __global__ __launch_bounds__(256) void msda_bwd_generic_h16(const H* __restrict_
   }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Fused front end (include/ocpg_hip.h: ocpg_msda_fused_*_h16): the 16-bit counterparts of msda_fwd_fused8 and
+// msda_bwd_gather_row<8, true> of msda.hip.  D = 32, L * P = 16; G = 4 lanes of 8 channels (default) or G = 8 lanes of 4.
+//
+// Sum 4 samples x {ga, gx, gy} over the 4 lanes of a row as a reduce-scatter inside the DPP quad: after it lane j holds sample j's
+// three totals (9 DPP moves; the all-reduce of row_sum<4> would take 24 and leave every lane with values three of them drop).
+__device__ __forceinline__ void reduce_scatter_g4_p4(const float (&v)[4][3], int j, float (&out)[3]) {
+  const bool hi = (j & 2) != 0;          // step 1: partner j^2; keep samples {0,1} or {2,3}
+  float a[2][3];
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float keep = hi ? v[2 + s][c] : v[s][c];
+      const float send = hi ? v[s][c] : v[2 + s][c];
+      a[s][c] = keep + dpp_xor2(send);
+    }
+  const bool lo = (j & 1) != 0;          // step 2: partner j^1; keep sample 0 or 1 of the pair
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float keep = lo ? a[1][c] : a[0][c];
+    const float send = lo ? a[0][c] : a[1][c];
+    out[c] = keep + dpp_xor1(send);
+  }
+}
+
+template <int G>
+__device__ __forceinline__ float row_max(float v) {
+  if constexpr (G == 4) {
+    v = fmaxf(v, dpp_xor1(v));
+    return fmaxf(v, dpp_xor2(v));
+  } else {
+#pragma unroll
+    for (int o = G / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+  }
+}
+
+// Fused forward.  qproj [N*Lq, 3*M*16] = [offsets (M, L, P, 2), already divided by (W_l, H_l) | logits (M, 16)], ref [N*Lq, L, 2]: lane j
+// of a row owns the samples j, j + G, ... in the set-up (softmax over the 16 logits, reference + offset, loc_out / attn_out written in
+// fp32, the sample records); the sampling loop is msda_fwd_h16's.
+template <typename H, int G, int CPL>
+__global__ __launch_bounds__(256) void msda_fwd_fused_h16(const H* __restrict__ value, const int64_t* __restrict__ shapes,
+                                                          const int64_t* __restrict__ level_start, const float* __restrict__ qproj,
+                                                          const float* __restrict__ ref, int S, int M, int L, int Lq, int P, long long rows,
+                                                          H* __restrict__ out, float* __restrict__ loc_out, float* __restrict__ attn_out) {
+  constexpr int D = CPL * G, ROWS = 256 / G, NS = 16, U = NS / G;
+  static_assert(D == 32 && (G == 4 || G == 8), "D = 32 as 4 x 8 or 8 x 4");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  SampleRec* recs = reinterpret_cast<SampleRec*>(smem);
+  __shared__ int lvlH[kMaxLevels], lvlW[kMaxLevels], lvlS[kMaxLevels];
+  const int tid = threadIdx.x;
+  if (tid < L) {
+    lvlH[tid] = (int)shapes[2 * tid];
+    lvlW[tid] = (int)shapes[2 * tid + 1];
+    lvlS[tid] = (int)level_start[tid];
+  }
+  __syncthreads();
+  const int MD = M * D;
+  const int r = tid / G, j = tid % G;
+  const long long qrow = (long long)(blockIdx.x / M) * ROWS + r;          // flat (b, q); head = block % M (one head per XCD L2)
+  const int m = blockIdx.x % M;
+  const long long row = qrow * M + m;
+  const bool live = qrow * M < rows;
+  if (live) {      // whole row groups are live or not (G divides 64): the DPP / shuffle exchanges stay within live groups
+    const int QW = 3 * M * NS;
+    const float* qo = qproj + qrow * QW + m * NS * 2;
+    const float* ql = qproj + qrow * QW + M * NS * 2 + m * NS;
+    float x[U], mx = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      x[u] = ql[j + u * G];
+      mx = fmaxf(mx, x[u]);
+    }
+    mx = row_max<G>(mx);
+    float e[U], part = 0.f;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      e[u] = expf(x[u] - mx);
+      part += e[u];
+    }
+    const float den = row_sum<G>(part);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int sidx = j + u * G, l = sidx / P;
+      const float a = e[u] / den;
+      const float2 off = *reinterpret_cast<const float2*>(qo + 2 * sidx);
+      const float2 rf = *reinterpret_cast<const float2*>(ref + (qrow * L + l) * 2);
+      const float lx = rf.x + off.x, ly = rf.y + off.y;
+      *reinterpret_cast<float2*>(loc_out + (row * NS + sidx) * 2) = make_float2(lx, ly);
+      attn_out[row * NS + sidx] = a;
+      SampleRec rec;
+      make_sample<float>(lx, ly, a, lvlH[l], lvlW[l], lvlS[l], MD, rec);
+      recs[r * NS + sidx] = rec;
+    }
+  }
+  __syncthreads();
+  if (!live) return;
+  const long long b = row / ((long long)Lq * M);
+  const H* vbase = value + b * (long long)S * MD + m * D + CPL * j;
+  float acc[CPL];
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) acc[c] = 0.f;
+  const SampleRec* rr = recs + r * NS;
+  for (int s = 0; s < NS; ++s) {
+    const SampleRec rec = rr[s];
+    if (rec.mask == 0) continue;  // uniform across the row's lanes
+    const float hy = 1.f - rec.ly, hx = 1.f - rec.lx;
+    // all four corners loaded (an outside corner from the row's own first pixel), raw words masked, widened after the loads: as msda_fwd_h16
+    const unsigned m1 = (rec.mask & 1) ? ~0u : 0u, m2 = (rec.mask & 2) ? ~0u : 0u, m3 = (rec.mask & 4) ? ~0u : 0u, m4 = (rec.mask & 8) ? ~0u : 0u;
+    const int o1 = rec.off00 & (int)m1, o2 = (rec.off00 + MD) & (int)m2, o3 = (rec.off00 + rec.rowstride) & (int)m3,
+              o4 = (rec.off00 + rec.rowstride + MD) & (int)m4;
+    const auto r1 = ocpg_dev::keep(ldraw<CPL>(vbase + o1), m1), r2 = ocpg_dev::keep(ldraw<CPL>(vbase + o2), m2),
+               r3 = ocpg_dev::keep(ldraw<CPL>(vbase + o3), m3), r4 = ocpg_dev::keep(ldraw<CPL>(vbase + o4), m4);
+    float v1[CPL], v2[CPL], v3[CPL], v4[CPL];
+    widen(r1, vbase, v1); widen(r2, vbase, v2); widen(r3, vbase, v3); widen(r4, vbase, v4);
+    const float w1 = hy * hx, w2 = hy * rec.lx, w3 = rec.ly * hx, w4 = rec.ly * rec.lx;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) acc[c] += (w1 * v1[c] + w2 * v2[c] + w3 * v3[c] + w4 * v4[c]) * rec.a;
+  }
+  stc<CPL>(out + row * D + CPL * j, acc);
+}
+
+// Fused gather: msda_bwd_gather_h16 whose epilogue applies the backward of the module's softmax and writes the gradient of the merged query
+// projection gq [N*Lq, 3*M*16] = [d offsets | d logits] instead of grad_loc / grad_attn.  Each sample's (d attn, d x, d y) totals stay
+// in registers across the four batches: with G = 8 the lane pair p = j >> 1 holds the samples 4k + p (reduce_scatter_g8_p4, as the fp32
+// kernel), with G = 4 lane j holds the samples 4k + j (reduce_scatter_g4_p4) and every lane stores.
+template <typename H, int G, int CPL>
+__global__ __launch_bounds__(256) void msda_bwd_gather_fused_h16(const H* __restrict__ value, const int64_t* __restrict__ shapes,
+                                                                 const int64_t* __restrict__ level_start, const float* __restrict__ loc,
+                                                                 const float* __restrict__ attn, const H* __restrict__ gout, int S, int M,
+                                                                 int L, int Lq, int P, long long rows, float* __restrict__ gq) {
+  constexpr int D = CPL * G, ROWS = 256 / G, NS = 16, NB = 4;
+  static_assert(D == 32 && (G == 4 || G == 8), "D = 32 as 4 x 8 or 8 x 4");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  GatherRec* recs = reinterpret_cast<GatherRec*>(smem);
+  __shared__ int lvlH[kMaxLevels], lvlW[kMaxLevels], lvlS[kMaxLevels];
+  const int tid = threadIdx.x;
+  if (tid < L) {
+    lvlH[tid] = (int)shapes[2 * tid];
+    lvlW[tid] = (int)shapes[2 * tid + 1];
+    lvlS[tid] = (int)level_start[tid];
+  }
+  __syncthreads();
+  const int MD = M * D;
+  const int r = tid / G, j = tid % G;
+  const long long qrow = (long long)(blockIdx.x / M) * ROWS + r;          // head fastest: one head per XCD L2
+  const int m = blockIdx.x % M;
+  const long long row = qrow * M + m;
+  const bool live = qrow * M < rows;
+  if (live) {
+    const float* lrow = loc + row * NS * 2;
+    const float* arow = attn + row * NS;
+    for (int s = j; s < NS; s += G) {
+      const int l = s / P;
+      GatherRec rec;
+      make_gather(lrow[2 * s], lrow[2 * s + 1], arow[s], lvlH[l], lvlW[l], lvlS[l], MD, rec);
+      recs[r * NS + s] = rec;
+    }
+  }
+  __syncthreads();
+  if (!live) return;  // whole row groups leave together (G divides 64): the DPP exchanges below stay within live groups
+  const long long b = row / ((long long)Lq * M);
+  const H* vbase = value + b * (long long)S * MD + m * D + CPL * j;
+  float go[CPL];
+  ldc<CPL>(gout + row * D + CPL * j, go);
+  const GatherRec* rr = recs + r * NS;
+  float fga[4] = {0.f, 0.f, 0.f, 0.f}, fgx[4] = {0.f, 0.f, 0.f, 0.f}, fgy[4] = {0.f, 0.f, 0.f, 0.f};      // this lane's sample of each batch
+  auto batch = [&](const int s0) {
+    float red[NB][3];
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const GatherRec rec = rr[s0 + i];
+      const int bits = rec.pk & 15;
+      const H* p00 = vbase + (rec.pk & ~15);
+      const int dx = (bits & 3) == 3 ? MD : 0, dy = (bits & 12) == 12 ? rec.rowstride : 0;
+      float v0[CPL], v1[CPL], v2[CPL], v3[CPL];
+      ldc<CPL>(p00, v0); ldc<CPL>(p00 + dx, v1); ldc<CPL>(p00 + dy, v2); ldc<CPL>(p00 + dy + dx, v3);
+      float d0 = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f;
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) { d0 += go[c] * v0[c]; d1 += go[c] * v1[c]; d2 += go[c] * v2[c]; d3 += go[c] * v3[c]; }
+      const float ix0 = (bits & 1) ? 1.f : 0.f, ix1 = (bits & 2) ? 1.f : 0.f, iy0 = (bits & 4) ? 1.f : 0.f, iy1 = (bits & 8) ? 1.f : 0.f;
+      const float top = rec.hx * d0 + rec.lx * d1, bot = rec.hx * d2 + rec.lx * d3;          // rows ya / yb, x-interpolated
+      const float lef = ix1 * d1 - ix0 * d0, rig = ix1 * d3 - ix0 * d2;                      // d/dx along rows ya / yb
+      red[i][0] = rec.hy * top + rec.ly * bot;
+      red[i][1] = rec.aW * (rec.hy * lef + rec.ly * rig);
+      red[i][2] = rec.aH * (iy1 * bot - iy0 * top);
+    }
+    float tot[3];
+    if constexpr (G == 8) (void)reduce_scatter_g8_p4(red, j, tot);
+    else reduce_scatter_g4_p4(red, j, tot);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {       // (selects, not an indexed store: the batch loop stays rolled)
+      const bool mine = s0 == NB * k;
+      fga[k] = mine ? tot[0] : fga[k]; fgx[k] = mine ? tot[1] : fgx[k]; fgy[k] = mine ? tot[2] : fgy[k];
+    }
+  };
+#pragma unroll 1
+  for (int s0 = 0; s0 < NS; s0 += NB) batch(s0);
+  // softmax backward over the row's 16 weights: d logit_s = a_s (ga_s - sum_t a_t ga_t)
+  const int p = G == 8 ? j >> 1 : j;
+  const bool owner = G == 4 || (j & 1) == 0;          // G = 8: both lanes of a pair hold the same totals, the even one counts and stores
+  float av[4], dotp = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    av[k] = attn[row * NS + 4 * k + p];
+    dotp += owner ? av[k] * fga[k] : 0.f;
+  }
+  const float dot = row_sum<G>(dotp);
+  if (owner) {
+    const int QW = 3 * M * NS;
+    float* go_ = gq + qrow * QW + m * (NS * 2);
+    float* gl_ = gq + qrow * QW + M * (NS * 2) + m * NS;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int sidx = 4 * k + p;
+      *reinterpret_cast<float2*>(go_ + 2 * sidx) = make_float2(fgx[k], fgy[k]);
+      gl_[sidx] = av[k] * (fga[k] - dot);
+    }
+  }
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------
 inline int pow2_group(int D, int cpl) {
   if (D % cpl) return 0;
@@ -574,6 +797,39 @@ int bwd_h16(const H* value, const int64_t* shapes, const int64_t* level_start, c
   return launch_status();
 }
 
+// ---- fused front end: D = 32, L * P = 16 only; both lane mappings fit the LDS (64 rows x 16 records x 32 B = 32 KB with 8 channels per lane)
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+inline bool fused_shape_ok(int S, int M, int D, int L, int P) {
+  return D == 32 && L * P == 16 && L <= kMaxLevels && (long long)S * M * D < (1LL << 31);
+}
+
+template <typename H>
+void launch_fused_fwd(const H* value, const int64_t* shapes, const int64_t* level_start, const float* qproj, const float* ref, int N, int S,
+                      int M, int L, int Lq, int P, H* out, float* loc_out, float* attn_out, hipStream_t st) {
+  const long long rows = (long long)N * Lq * M;
+  const int G = 32 / lanes_cpl(MSDA_H16_FWD_CPL), rpb = 256 / G;
+  const unsigned grid = (unsigned)((((long long)N * Lq + rpb - 1) / rpb) * M);
+  const size_t lds = rpb * (size_t)16 * sizeof(SampleRec);
+  if (G == 4)
+    msda_fwd_fused_h16<H, 4, 8><<<grid, 256, lds, st>>>(value, shapes, level_start, qproj, ref, S, M, L, Lq, P, rows, out, loc_out, attn_out);
+  else
+    msda_fwd_fused_h16<H, 8, 4><<<grid, 256, lds, st>>>(value, shapes, level_start, qproj, ref, S, M, L, Lq, P, rows, out, loc_out, attn_out);
+}
+
+template <typename H>
+void launch_fused_gather(const H* value, const int64_t* shapes, const int64_t* level_start, const float* loc, const float* attn,
+                         const H* grad_out, int N, int S, int M, int L, int Lq, int P, float* grad_qproj, hipStream_t st) {
+  const long long rows = (long long)N * Lq * M;
+  const int G = 32 / lanes_cpl(MSDA_H16_GATHER_CPL), rpb = 256 / G;
+  const unsigned grid = (unsigned)((((long long)N * Lq + rpb - 1) / rpb) * M);
+  const size_t lds = rpb * (size_t)16 * sizeof(GatherRec);
+  if (G == 4)
+    msda_bwd_gather_fused_h16<H, 4, 8><<<grid, 256, lds, st>>>(value, shapes, level_start, loc, attn, grad_out, S, M, L, Lq, P, rows, grad_qproj);
+  else
+    msda_bwd_gather_fused_h16<H, 8, 4><<<grid, 256, lds, st>>>(value, shapes, level_start, loc, attn, grad_out, S, M, L, Lq, P, rows, grad_qproj);
+}
+
 }  // namespace
 
 extern "C" {
@@ -642,6 +898,50 @@ int ocpg_msda_bwd_locattn_h16(const void* value, const int64_t* shapes, const in
   else
     launch_gather(cpl, static_cast<const fp16s*>(value), shapes, level_start, loc, attn, static_cast<const fp16s*>(grad_out), N, S, M, D, L, Lq, P,
                   grad_loc, grad_attn, st);
+  return launch_status();
+}
+
+// ---- fused front end (include/ocpg_hip.h): -2000 = shape or alignment not served, settled for every pointer before anything is launched ----
+int ocpg_msda_fused_fwd_h16(const void* value, const int64_t* shapes, const int64_t* level_start, const float* qproj, const float* ref,
+                            int N, int S, int M, int D, int L, int Lq, int P, void* out, float* loc_out, float* attn_out, int dtype,
+                            void* stream) {
+  if (int e = check_common(value, shapes, level_start, qproj, ref, N, S, M, D, L, Lq, P)) return e;
+  if (dtype != 1 && dtype != 2) return -1016;
+  if ((long long)N * Lq * M == 0) return 0;
+  if (!out) return -1013;
+  if (!loc_out) return -1014;
+  if (!attn_out) return -1015;
+  if (!fused_shape_ok(S, M, D, L, P)) return -2000;
+  // 16-byte (8 channels) / 8-byte (4 channels) accesses to value and out: 16 asked of both mappings, as the un-fused kernels do; float2
+  // accesses to the offsets, the reference points and loc_out
+  if (!aligned16(value) || !aligned16(out) || !aligned8(qproj) || !aligned8(ref) || !aligned8(loc_out)) return -2000;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == 1)
+    launch_fused_fwd(static_cast<const bf16s*>(value), shapes, level_start, qproj, ref, N, S, M, L, Lq, P, static_cast<bf16s*>(out), loc_out,
+                     attn_out, st);
+  else
+    launch_fused_fwd(static_cast<const fp16s*>(value), shapes, level_start, qproj, ref, N, S, M, L, Lq, P, static_cast<fp16s*>(out), loc_out,
+                     attn_out, st);
+  return launch_status();
+}
+
+int ocpg_msda_fused_bwd_qproj_h16(const void* value, const int64_t* shapes, const int64_t* level_start, const float* loc, const float* attn,
+                                  const void* grad_out, int N, int S, int M, int D, int L, int Lq, int P, float* grad_qproj, int dtype,
+                                  void* stream) {
+  if (int e = check_common(value, shapes, level_start, loc, attn, N, S, M, D, L, Lq, P)) return e;
+  if (dtype != 1 && dtype != 2) return -1015;
+  if ((long long)N * Lq * M == 0) return 0;
+  if (!grad_out) return -1013;
+  if (!grad_qproj) return -1014;
+  if (!fused_shape_ok(S, M, D, L, P)) return -2000;
+  if (!aligned16(value) || !aligned16(grad_out) || !aligned8(grad_qproj)) return -2000;       // (loc / attn are read one float at a time)
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == 1)
+    launch_fused_gather(static_cast<const bf16s*>(value), shapes, level_start, loc, attn, static_cast<const bf16s*>(grad_out), N, S, M, L, Lq, P,
+                        grad_qproj, st);
+  else
+    launch_fused_gather(static_cast<const fp16s*>(value), shapes, level_start, loc, attn, static_cast<const fp16s*>(grad_out), N, S, M, L, Lq, P,
+                        grad_qproj, st);
   return launch_status();
 }
 

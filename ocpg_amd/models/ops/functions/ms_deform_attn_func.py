@@ -205,18 +205,22 @@ class MSDeformAttnFunction(Function):
 
 
 class MSDeformAttnFusedFunction(Function):
-    """The module's front end fused into the op (include/ocpg_hip.h: ocpg_msda_fused_fwd_f32 / _bwd_qproj_f32): softmax over the L*P logits
-    and `reference + offset` (ms_deform_attn.py:96-110, 2-d reference branch) inside the forward kernel's sample setup, the softmax backward
-    and the [d offsets | d logits] layout inside the gather kernel's epilogue.  Self-attention calls only (Lq == S), D = 32, L*P = 16,
-    reference points without gradient; `supported()` says whether a call qualifies -- the module keeps the unfused path otherwise.
-    fp32 only: the fused kernels have no 16-bit-storage form, so a bfloat16 / float16 value is not supported here and takes the unfused op.
+    """The module's front end fused into the op (include/ocpg_hip.h: ocpg_msda_fused_fwd_f32 / _bwd_qproj_f32 and their _h16 forms): softmax
+    over the L*P logits and `reference + offset` (ms_deform_attn.py:96-110, 2-d reference branch) inside the forward kernel's sample setup,
+    the softmax backward and the [d offsets | d logits] layout inside the gather kernel's epilogue.  Self-attention calls only (Lq == S),
+    D = 32, L*P = 16, reference points without gradient; `supported()` says whether a call qualifies -- the module keeps the unfused path
+    otherwise.
+    value is float32, or bfloat16 / float16 (16-bit STORAGE of value / out / grad_out): qproj, ref and the returned loc / attn are float32
+    in every case, out has value's dtype, grad_output must arrive in value's dtype, grad_value is accumulated in an fp32 buffer and
+    handed back in value's dtype.  A 16-bit call the fused kernels decline (-2000: a buffer off the alignment their vector accesses need)
+    is served by the un-fused 16-bit entry points with the front end in torch: same results, no exception.
 
     apply(value [N,S,M,D], shapes, level_start, qproj [N,Lq,3*M*L*P], ref [N,Lq,L,2], L, P, sel_state) -> (out, loc, attn)"""
 
     @staticmethod
     def supported(value, qproj, ref, L, P):
-        return (value.is_cuda and value.dtype == torch.float32 and qproj.dtype == torch.float32 and ref.dtype == torch.float32
-                and value.shape[-1] == 32 and L * P == 16 and ref.shape[-1] == 2 and not ref.requires_grad
+        return (value.is_cuda and (value.dtype == torch.float32 or value.dtype in _H16) and qproj.dtype == torch.float32
+                and ref.dtype == torch.float32 and value.shape[-1] == 32 and L * P == 16 and ref.shape[-1] == 2 and not ref.requires_grad
                 and value.shape[1] == qproj.shape[1] and qproj.is_contiguous())
 
     @staticmethod
@@ -225,12 +229,24 @@ class MSDeformAttnFusedFunction(Function):
         Lq = qproj.shape[1]
         value, ref = value.contiguous(), ref.contiguous()
         out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
-        loc = torch.empty((N, Lq, M, L, P, 2), dtype=value.dtype, device=value.device)
-        attn = torch.empty((N, Lq, M, L, P), dtype=value.dtype, device=value.device)
+        loc = torch.empty((N, Lq, M, L, P, 2), dtype=torch.float32, device=value.device)
+        attn = torch.empty((N, Lq, M, L, P), dtype=torch.float32, device=value.device)
         with torch.cuda.device(value.device), _timed("fwd_enc"):
-            check(lib().ocpg_msda_fused_fwd_f32(value.data_ptr(), shapes.data_ptr(), level_start.data_ptr(), qproj.data_ptr(), ref.data_ptr(),
-                                                N, S, M, D, L, Lq, P, out.data_ptr(), loc.data_ptr(), attn.data_ptr(), stream_ptr()),
-                  "ocpg_msda_fused_fwd")
+            if value.dtype in _H16:
+                code = _H16[value.dtype]
+                rc = lib().ocpg_msda_fused_fwd_h16(value.data_ptr(), shapes.data_ptr(), level_start.data_ptr(), qproj.data_ptr(), ref.data_ptr(),
+                                                   N, S, M, D, L, Lq, P, out.data_ptr(), loc.data_ptr(), attn.data_ptr(), code, stream_ptr())
+                if rc == -2000:        # declined, nothing launched: the front end in torch, the un-fused 16-bit forward
+                    off, logit = torch.split(qproj.view(N, Lq, -1), [2 * M * L * P, M * L * P], dim=-1)
+                    attn = torch.softmax(logit.reshape(N, Lq, M, L * P), -1).view(N, Lq, M, L, P)
+                    loc = (ref.view(N, Lq, 1, L, 1, 2) + off.reshape(N, Lq, M, L, P, 2)).contiguous()
+                    rc = lib().ocpg_msda_fwd_h16(value.data_ptr(), shapes.data_ptr(), level_start.data_ptr(), loc.data_ptr(), attn.data_ptr(),
+                                                 N, S, M, D, L, Lq, P, out.data_ptr(), None, code, stream_ptr())
+                check(rc, "ocpg_msda_fused_fwd_h16")
+            else:
+                check(lib().ocpg_msda_fused_fwd_f32(value.data_ptr(), shapes.data_ptr(), level_start.data_ptr(), qproj.data_ptr(), ref.data_ptr(),
+                                                    N, S, M, D, L, Lq, P, out.data_ptr(), loc.data_ptr(), attn.data_ptr(), stream_ptr()),
+                      "ocpg_msda_fused_fwd")
         ctx.save_for_backward(value, shapes, level_start, loc, attn)
         ctx.shapes_host = getattr(shapes, "_ocpg_host", None)
         ctx.sel_state = sel_state
@@ -246,6 +262,8 @@ class MSDeformAttnFusedFunction(Function):
         _, Lq, _, L, P, _ = loc.shape
         go = grad_output.contiguous()
         hs = ctx.shapes_host if ctx.shapes_host is not None else _host_shapes(shapes)
+        if value.dtype in _H16:
+            return MSDeformAttnFusedFunction._backward_h16(ctx, value, shapes, level_start, loc, attn, go, hs)
         grad_value = torch.zeros_like(value)
         grad_q = torch.empty(ctx.qshape, dtype=value.dtype, device=value.device)
         L_ = lib()
@@ -270,3 +288,40 @@ class MSDeformAttnFusedFunction(Function):
                 check(L_.ocpg_msda_fused_bwd_qproj_f32(value.data_ptr(), shapes.data_ptr(), level_start.data_ptr(), loc.data_ptr(), attn.data_ptr(),
                                                        go.data_ptr(), N, S, M, D, L, Lq, P, grad_q.data_ptr(), stream_ptr()), "ocpg_msda_fused_bwd_qproj")
         return grad_value, None, None, grad_q, None, None, None, None
+
+    @staticmethod
+    def _backward_h16(ctx, value, shapes, level_start, loc, attn, go, hs):
+        """16-bit storage: grad_value from ocpg_msda_bwd_value_h16 (fp32 accumulation, the call site's path selection), grad_qproj from the
+        fused gather; when either declines (-2000, nothing launched) the whole backward goes through ocpg_msda_bwd_h16 and the softmax
+        backward / concatenation happen in torch, as in the fp32 function."""
+        N, S, M, D = value.shape
+        _, Lq, _, L, P, _ = loc.shape
+        if go.dtype != value.dtype:
+            raise RuntimeError(f"MSDeformAttnFusedFunction: grad_output must have value's dtype {value.dtype} (got {go.dtype})")
+        code = _H16[value.dtype]
+        grad_value = torch.zeros(value.shape, dtype=torch.float32, device=value.device)
+        grad_q = torch.empty(ctx.qshape, dtype=torch.float32, device=value.device)
+        sel = ctx.sel_state.data_ptr() if ctx.sel_state is not None else None
+        hsp = ctypes.c_void_p(hs.data_ptr())
+        L_ = lib()
+        with torch.cuda.device(value.device):
+            with _timed("bwd_enc_value"):
+                rc = L_.ocpg_msda_bwd_value_h16(loc.data_ptr(), attn.data_ptr(), go.data_ptr(), N, S, M, D, L, Lq, P, grad_value.data_ptr(), hsp, sel,
+                                                code, stream_ptr())
+            if rc == 0:
+                with _timed("bwd_enc_locattn"):
+                    rc = L_.ocpg_msda_fused_bwd_qproj_h16(value.data_ptr(), shapes.data_ptr(), level_start.data_ptr(), loc.data_ptr(), attn.data_ptr(),
+                                                          go.data_ptr(), N, S, M, D, L, Lq, P, grad_q.data_ptr(), code, stream_ptr())
+                if rc == -2000:
+                    grad_value.zero_()         # the scatter has run: start the accumulation over
+            if rc == -2000:
+                gl, ga = torch.empty_like(loc), torch.empty_like(attn)
+                with _timed("bwd_enc"):
+                    check(L_.ocpg_msda_bwd_h16(value.data_ptr(), shapes.data_ptr(), level_start.data_ptr(), loc.data_ptr(), attn.data_ptr(), go.data_ptr(),
+                                               N, S, M, D, L, Lq, P, grad_value.data_ptr(), gl.data_ptr(), ga.data_ptr(), hsp, sel, code, stream_ptr()),
+                          "ocpg_msda_bwd_h16")
+                glogit = attn.view(N, Lq, M, L * P) * (ga.view(N, Lq, M, L * P) - (attn * ga).view(N, Lq, M, L * P).sum(-1, keepdim=True))
+                grad_q = torch.cat([gl.reshape(N, Lq, -1), glogit.reshape(N, Lq, -1)], -1).view(ctx.qshape)
+            else:
+                check(rc, "ocpg_msda_fused_bwd_h16")
+        return grad_value.to(value.dtype), None, None, grad_q, None, None, None, None

@@ -21,6 +21,9 @@ from ..functions.ms_deform_attn_func import MSDeformAttnFusedFunction
 
 
 FUSED_FRONT = os.environ.get("OCPG_MSDA_FUSED_FRONT", "1") != "0"   # A/B switch: softmax + location arithmetic (and their backward) inside the op's kernels
+# the same front end for the opt-in 16-bit value path (ocpg_msda_fused_*_h16).  Off unless OCPG_MSDA_FUSED_FRONT_H16 is set to something but "0":
+# the 16-bit mode's default stays the un-fused op
+FUSED_FRONT_H16 = os.environ.get("OCPG_MSDA_FUSED_FRONT_H16", "0") != "0"
 SELECT_PATH = os.environ.get("OCPG_MSDA_SELECT", "1") != "0"     # A/B switch: per-call choice of the grad_value kernel family (self-attention calls)
 MERGED_QUERY_PROJ = True      # A/B switch: sampling_offsets and attention_weights as ONE GEMM over the query (they share their input)
 
@@ -148,12 +151,13 @@ class MSDeformAttn(nn.Module):
                            .expand(M, L, P, 2).reshape(-1).to(query.device))
                 so_w, so_b = so_w * inv[:, None], so_b * inv
             both = linear(query, torch.cat([so_w, self.attention_weights.weight], 0), torch.cat([so_b, self.attention_weights.bias], 0))
-            # (a 16-bit value is not `supported`: the fused kernels are fp32 only, the un-fused op below has the 16-bit form)
-            if (FUSED_FRONT and folded and Lq == S and MSDeformAttnFusedFunction.supported(value, both, reference_points, L, P)):
+            # (each value dtype has its own switch: the fp32 front end is on by default, the 16-bit one is opt-in)
+            if ((FUSED_FRONT if vd is None else FUSED_FRONT_H16) and folded and Lq == S
+                    and MSDeformAttnFusedFunction.supported(value, both, reference_points, L, P)):
                 # lines 96-110 of the reference module inside the kernels: no softmax / add / split-cat passes over the [N, Lq, 384] projection
                 out, loc, weights = MSDeformAttnFusedFunction.apply(value.contiguous(), input_spatial_shapes, input_level_start_index, both,
                                                                     reference_points, L, P, self._sel_state if SELECT_PATH else None)
-                return self.output_proj(out), loc, weights
+                return (self.output_proj(out) if vd is None else self._linear16(out, self.output_proj, vd)), loc, weights
             off2, logit2 = torch.split(both, [n_off, M * L * P], dim=-1)      # split: its backward is ONE cat (two slices: 2 x (zeros + copy) + add)
             offsets = off2.view(N, Lq, M, L, P, 2)
             weights = F.softmax(logit2.view(N, Lq, M, L * P), -1).view(N, Lq, M, L, P)

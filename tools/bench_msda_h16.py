@@ -3,6 +3,8 @@ forward, gather half (grad_loc / grad_attn) and scatter half (grad_value) of the
 operands, HIP events around the C-ABI call only, on
   ring     the model's initial offsets,
   trained  ring + N(0, 3 px) + 5 % far outliers (the "trained-like" offsets of tools/bench_msda_gv.py).
+The fused front end of the 16-bit path (ocpg_msda_fused_fwd_h16 / ocpg_msda_fused_bwd_qproj_h16: kernels "fwd_fused" / "gather_fused") is
+timed in the same rounds, next to the un-fused 16-bit kernels it replaces, on the same locations and weights (qproj = [loc - ref | log attn]).
 The 16-bit forward and gather run with 4 channels per lane (8-byte loads, variant a) and 8 (16-byte loads, variant b); at this shape
 (D = 32, L * P = 16) the library honours both requests (for shapes whose records do not fit the LDS it serves 8 as 4).
 --launches per kernel and round (default 200), --rounds (default 3: the spread over the rounds is the yardstick of "not slower").
@@ -71,11 +73,22 @@ BYTES = {   # algorithmic: every operand once
     ("fwd", 4): 4 * n_val + 12 * n_samp + 4 * n_val, ("fwd", 2): 2 * n_val + 12 * n_samp + 2 * n_val,
     ("gather", 4): 4 * n_val + 12 * n_samp + 4 * n_val + 12 * n_samp, ("gather", 2): 2 * n_val + 12 * n_samp + 2 * n_val + 12 * n_samp,
     ("scatter", 4): 12 * n_samp + 4 * n_val + 4 * n_val, ("scatter", 2): 12 * n_samp + 2 * n_val + 4 * n_val,
+    # fused front end: value + out + qproj read + loc / attn written + ref;  value + loc / attn + grad_out read + grad_qproj written
+    ("fwd_fused", 2): 2 * n_val + 2 * n_val + 12 * n_samp + 12 * n_samp + 4 * N * S * L * 2,
+    ("gather_fused", 2): 2 * n_val + 12 * n_samp + 2 * n_val + 12 * n_samp,
 }
 
 
 def calls(loc):
     gl, ga = torch.empty_like(loc), torch.empty_like(attn)
+    # the fused front end's inputs for the same samples: every query's own pixel centre as reference point on every level
+    refs = []
+    for (h, w) in shapes_l:
+        ys, xs = torch.meshgrid(torch.linspace(0.5, h - 0.5, h) / h, torch.linspace(0.5, w - 0.5, w) / w, indexing="ij")
+        refs.append(torch.stack([xs.reshape(-1), ys.reshape(-1)], -1))
+    ref = torch.cat(refs, 0)[None, :, None, :].expand(N, S, L, 2).contiguous().to(dev)
+    qproj = torch.cat([(loc - ref[:, :, None, :, None, :]).reshape(N, S, -1), attn.log().reshape(N, S, -1)], -1).contiguous()
+    loc_o, attn_o, gq = torch.empty_like(loc), torch.empty_like(attn), torch.empty_like(qproj)
     L_ = lib()
     p = lambda t: t.data_ptr()
     return {
@@ -83,9 +96,12 @@ def calls(loc):
         ("fwd", "h16"): lambda: L_.ocpg_msda_fwd_h16(p(v16), p(ds), p(dls), p(loc), p(attn), *dims, p(out16), None, code, stream_ptr()),
         ("gather", "fp32"): lambda: L_.ocpg_msda_bwd_locattn_f32(p(v32), p(ds), p(dls), p(loc), p(attn), p(go32), *dims, p(gl), p(ga), stream_ptr()),
         ("gather", "h16"): lambda: L_.ocpg_msda_bwd_locattn_h16(p(v16), p(ds), p(dls), p(loc), p(attn), p(go16), *dims, p(gl), p(ga), code, stream_ptr()),
+        ("fwd_fused", "h16"): lambda: L_.ocpg_msda_fused_fwd_h16(p(v16), p(ds), p(dls), p(qproj), p(ref), *dims, p(out16), p(loc_o), p(attn_o), code,
+                                                                 stream_ptr()),
+        ("gather_fused", "h16"): lambda: L_.ocpg_msda_fused_bwd_qproj_h16(p(v16), p(ds), p(dls), p(loc), p(attn), p(go16), *dims, p(gq), code, stream_ptr()),
         ("scatter", "fp32"): lambda: L_.ocpg_msda_bwd_value_f32(p(loc), p(attn), p(go32), *dims, p(gv), hs, stream_ptr()),
         ("scatter", "h16"): lambda: L_.ocpg_msda_bwd_value_h16(p(loc), p(attn), p(go16), *dims, p(gv), hs, None, code, stream_ptr()),
-    }, (gl, ga)
+    }, (gl, ga, ref, qproj, loc_o, attn_o, gq)
 
 
 def timed(fn, n, zero):
@@ -101,8 +117,9 @@ def timed(fn, n, zero):
     return sorted(e0.elapsed_time(e1) * 1e3 for e0, e1 in ev)[n // 2]
 
 
-VARIANTS = [("fwd", "fp32", None), ("fwd", "h16", "4"), ("fwd", "h16", "8"), ("gather", "fp32", None), ("gather", "h16", "4"),
-            ("gather", "h16", "8"), ("scatter", "fp32", None), ("scatter", "h16", None)]
+VARIANTS = [("fwd", "fp32", None), ("fwd", "h16", "4"), ("fwd_fused", "h16", "4"), ("fwd", "h16", "8"), ("fwd_fused", "h16", "8"),
+            ("gather", "fp32", None), ("gather", "h16", "4"), ("gather_fused", "h16", "4"), ("gather", "h16", "8"), ("gather_fused", "h16", "8"),
+            ("scatter", "fp32", None), ("scatter", "h16", None)]
 for mode, noise, outl in (("ring", 0.0, 0.0), ("trained", 3.0, 0.05)):
     loc = ring_loc(noise, outl).to(dev)
     fns, keep = calls(loc)
