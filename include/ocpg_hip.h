@@ -179,7 +179,8 @@ int ocpg_msda_fused_bwd_qproj_h16(const void* value, const int64_t* shapes, cons
  * torchvision Bottleneck's "out += identity" / ReLU.  scale/shift are the per-channel fp32 vectors [C].
  *   y[o,c,i] = act(x[o,c,i] * scale[c] + shift[c] (+ skip[o,c,i])),  element (o,c,i) at ((o*C + c)*inner + i)
  *   NHWC / channels_last: n_outer = N*H*W, inner = 1;   NCHW: n_outer = N, inner = H*W.
- * dtype: 0 = float32, 1 = bfloat16 (storage; arithmetic is fp32).  skip may be NULL.  y may alias x.
+ * dtype: 0 = float32, 1 = bfloat16, 2 = float16 (storage; arithmetic is fp32; narrowing rounds to nearest even, NaN / inf pass through and
+ * an fp16 overflow becomes inf as in ATen: no saturation); anything else: -1010.  skip may be NULL.  y may alias x.
  * Backward needs only the saved OUTPUT y: g = relu ? (y > 0 ? gy : 0) : gy; gx = g*scale[c]; gskip = g.
  * gx or gskip may be NULL (not wanted); gskip may alias gy. */
 int ocpg_bn_act_fwd(const void* x, const float* scale, const float* shift, const void* skip, void* y,
@@ -187,7 +188,7 @@ int ocpg_bn_act_fwd(const void* x, const float* scale, const float* shift, const
 int ocpg_bn_act_bwd(const void* gy, const void* y, const float* scale, void* gx, void* gskip,
                     long long n_outer, int C, long long inner, int relu, int dtype, void* stream);
 
-/* Input gradient of a 1x1 convolution (channels-last bf16) with the frozen-BN + ReLU backward of the layer in front in its epilogue
+/* Input gradient of a 1x1 convolution (channels-last bf16 or fp16) with the frozen-BN + ReLU backward of the layer in front in its epilogue
  * (csrc/gemm_dgrad_bn.hip; MFMA, fp32 accumulation): replaces ocpg_gemm (input gradient) + ocpg_bn_act_bwd of the layer in front.
  *   v[m,n] = sum_k a[m,k] w[k,n]         a [M,K] (the gradient after this convolution's BN backward), w [K = Cout][N = Cin] as it lies
  *   v += c[m,n]                          c may be NULL; the block's parked identity-skip gradient
@@ -197,7 +198,7 @@ int ocpg_bn_act_bwd(const void* gy, const void* y, const float* scale, void* gx,
  * tile: 0 = 128 x 128, 1 = 64 x 128, 2 = 64 x 64 workgroup tiles; ocpg_gemm_dgrad_bn_tile returns the measured-best one (64 x 64) or -1
  * (the shape is not served).  Deterministic; every tile gives the same bits.
  * Declined (the caller keeps its GEMM + ocpg_bn_act_bwd): -2000 shape (N % tile width, K % 128), -2001 a pointer not 16-byte aligned,
- * -2002 dtype other than 1 (bf16). */
+ * -2002 dtype other than 1 (bf16) or 2 (fp16: its own instantiations, MFMA 32x32x16 f16; `bf16(...)` above then reads fp16(...)). */
 int ocpg_gemm_dgrad_bn_tile(long long M, int N, int K);
 int ocpg_gemm_dgrad_bn(const void* a, const void* w, const void* c, const void* mask, const float* scale, void* out, void* out_skip,
                        long long M, int N, int K, int dtype, int tile, void* stream);
@@ -298,6 +299,19 @@ int ocpg_conv3x3_mfma_dgrad_w_splitk(const void* dy, const void* w, const void* 
                                      int Cout, int stride, int splits, float* part, void* dx, void* stream);
 int ocpg_conv3x3_mfma_wgrad_splits(int N, int H, int W, int Cin, int Cout, int stride);
 int ocpg_conv3x3_mfma_wgrad(const void* gz, const void* x, int N, int H, int W, int Cin, int Cout, int stride, void* part, void* stream);
+/* The three entry points of the shipped step with the 16-bit STORAGE TYPE as an argument (the reference's --amp mode is fp16:
+ * engine.py amp.autocast + GradScaler): dtype 1 = bfloat16, 2 = float16 (the numbering of ocpg_bn_act_* and of the MSDeformAttn _h16 entry
+ * points); any other value returns -1010 before anything is launched.  Arguments, geometry limits and return codes are those of the
+ * un-suffixed twin, every tensor (x, w, y, cols / dy, mask_y, dx / gz, part) in that one type; scale / bias stay fp32 and the accumulation
+ * fp32.  With dtype 1 they launch the very kernels the un-suffixed symbols launch (which forward here); with dtype 2 the fp16 instantiations
+ * (MFMA 32x32x16 f16).  ocpg_conv3x3_mfma_wgrad_splits serves both.  The split-K forms, ocpg_conv3x3_mfma_dgrad(_masked) and the halo
+ * variant have no fp16 form. */
+int ocpg_conv3x3_mfma_fwd_cols_h16(const void* x, const void* w, const float* scale, const float* bias, int relu, int N, int H, int W, int Cin,
+                                   int Cout, int stride, void* y, void* cols, int dtype, void* stream);
+int ocpg_conv3x3_mfma_dgrad_w_h16(const void* dy, const void* w, const void* mask_y, const float* scale, int N, int H, int W, int Cin, int Cout,
+                                  int stride, void* dx, int dtype, void* stream);
+int ocpg_conv3x3_mfma_wgrad_h16(const void* gz, const void* x, int N, int H, int W, int Cin, int Cout, int stride, void* part, int dtype,
+                                void* stream);
 
 /* Split-K form of ocpg_conv3x3_mfma_fwd for convolutions with FEW output pixels and a LONG reduction (round 4): the neck's extra level
  * input_proj[3] = nn.Conv2d(2048, 256, 3, stride=2, padding=1) (models/ocpg.py:119-123; 600 output pixels at config #2, K = 18 432) --

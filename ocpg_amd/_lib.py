@@ -51,6 +51,9 @@ SIGNATURES = {
     "ocpg_conv3x3_mfma_fwd_bn_splitk": [_vp, _vp, _vp, _vp] + [_int] * 8 + [_vp, _vp, _vp],
     "ocpg_conv3x3_mfma_dgrad_w_splitk": [_vp, _vp, _vp, _vp] + [_int] * 7 + [_vp, _vp, _vp],
     "ocpg_conv3x3_mfma_wgrad": [_vp, _vp] + [_int] * 6 + [_vp, _vp],
+    "ocpg_conv3x3_mfma_fwd_cols_h16": [_vp, _vp, _vp, _vp] + [_int] * 7 + [_vp, _vp, _int, _vp],
+    "ocpg_conv3x3_mfma_dgrad_w_h16": [_vp, _vp, _vp, _vp] + [_int] * 6 + [_vp, _int, _vp],
+    "ocpg_conv3x3_mfma_wgrad_h16": [_vp, _vp] + [_int] * 6 + [_vp, _int, _vp],
     "ocpg_conv3x3_mfma_fwd_splitk": [_vp, _vp, _vp] + [_int] * 7 + [_vp, _vp, _int, _vp, _vp],
     "ocpg_gemm": [_vp, _vp, _vp, _vp] + [_int] * 4 + [ctypes.c_longlong] * 10 + [ctypes.c_float, ctypes.c_float, _vp],
     "ocpg_gemm_plans": [],

@@ -3,11 +3,12 @@
 // Reference arithmetic: FrozenBatchNorm2d.forward (models/backbone.py:46-56): y = x * scale[c] + shift[c] with
 // scale = w * rsqrt(var + 1e-5), shift = b - mean * scale, followed in torchvision's Bottleneck by ReLU, or by
 // "+ identity" then ReLU.  The reference runs that as 4 + 1 (+1) elementwise kernels per BN; 104 BNs in ResNet-101.
-// Here: y = act(x * scale[c] + shift[c] (+ skip)), 16 bytes per lane, fp32 math, bf16 or fp32 storage;
+// Here: y = act(x * scale[c] + shift[c] (+ skip)), 16 bytes per lane, fp32 math, fp32, bf16 or fp16 storage;
 // backward from the saved OUTPUT only: g = relu ? (y > 0 ? gy : 0) : gy;  gx = g * scale[c];  gskip = g.
 // Layout: element (o, c, i) lives at ((o * C + c) * inner + i):  NHWC (channels_last): inner = 1, o = pixel;
 // NCHW: inner = H*W, o = image.  HBM-bound streaming kernel: 2-3 tensors in, 1-2 out, nothing re-read.
 #include <hip/hip_bf16.h>
+#include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -54,6 +55,31 @@ struct Vec<__hip_bfloat16> {
   }
   static __device__ __forceinline__ float get(const __hip_bfloat16* p) { return __bfloat162float(*p); }
   static __device__ __forceinline__ void put(__hip_bfloat16* p, float v) { *p = __float2bfloat16(v); }
+};
+// fp16 storage (the reference's --amp mode): plain widening, round-to-nearest-even narrowing; NaN / inf pass through and a value past
+// 65504 becomes inf as in ATen (the GradScaler's business, no saturation here)
+template <>
+struct Vec<__half> {
+  static constexpr int N = 8;
+  static __device__ __forceinline__ void load(const __half* p, float (&f)[8]) {
+    const uint4 v = *reinterpret_cast<const uint4*>(p);
+    const __half2* h = reinterpret_cast<const __half2*>(&v);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float2 t = __half22float2(h[i]);
+      f[2 * i] = t.x;
+      f[2 * i + 1] = t.y;
+    }
+  }
+  static __device__ __forceinline__ void store(__half* p, const float (&f)[8]) {
+    uint4 v;
+    __half2* h = reinterpret_cast<__half2*>(&v);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) h[i] = __floats2half2_rn(f[2 * i], f[2 * i + 1]);
+    *reinterpret_cast<uint4*>(p) = v;
+  }
+  static __device__ __forceinline__ float get(const __half* p) { return __half2float(*p); }
+  static __device__ __forceinline__ void put(__half* p, float v) { *p = __float2half_rn(v); }
 };
 
 // MODE 0: inner == 1 (NHWC), C % N == 0: a vector spans N consecutive channels.
@@ -198,6 +224,7 @@ int ocpg_bn_act_fwd(const void* x, const float* scale, const float* shift, const
   if (!y) return -1005;
   if (dtype == 0) return launch_fwd<float>(x, scale, shift, skip, y, n_outer, C, inner, relu, (hipStream_t)stream);
   if (dtype == 1) return launch_fwd<__hip_bfloat16>(x, scale, shift, skip, y, n_outer, C, inner, relu, (hipStream_t)stream);
+  if (dtype == 2) return launch_fwd<__half>(x, scale, shift, skip, y, n_outer, C, inner, relu, (hipStream_t)stream);
   return -1010;
 }
 
@@ -210,6 +237,7 @@ int ocpg_bn_act_bwd(const void* gy, const void* y, const float* scale, void* gx,
   if (!scale) return -1003;
   if (dtype == 0) return launch_bwd<float>(gy, y, scale, gx, gskip, n_outer, C, inner, relu, (hipStream_t)stream);
   if (dtype == 1) return launch_bwd<__hip_bfloat16>(gy, y, scale, gx, gskip, n_outer, C, inner, relu, (hipStream_t)stream);
+  if (dtype == 2) return launch_bwd<__half>(gy, y, scale, gx, gskip, n_outer, C, inner, relu, (hipStream_t)stream);
   return -1010;
 }
 

@@ -1,5 +1,5 @@
 // Input gradient of a 1x1 convolution of the ResNet body WITH the frozen-BN + ReLU backward of the layer in front in its epilogue
-// (gfx950 MFMA 32x32x16 bf16, fp32 accumulation).  Until now each such site was a hipBLASLt GEMM (no ReLU-mask epilogue there)
+// (gfx950 MFMA 32x32x16 bf16 or f16, fp32 accumulation).  Until now each such site was a hipBLASLt GEMM (no ReLU-mask epilogue there)
 // followed by a pure memory pass, ocpg_bn_act_bwd (csrc/bn_act.hip): 57 of its 63 launches per step sat right behind one of these GEMMs.
 //
 // GEMM view (channels-last maps, the 1x1 weight as it lies):
@@ -18,16 +18,18 @@
 // through LDS so that every thread handles 8 consecutive columns of one row: 16-byte loads of C and the mask, 16-byte stores.  Every
 // output element is one fp32 chain over k in ascending order, whatever the tile: deterministic, and the same bits for every tile.
 #include <hip/hip_bf16.h>
+#include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/ocpg_hip.h"
+#include "h16_elem.h"
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
+typedef ocpg_h16::h16x8 bf16x8;
 typedef short s4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef ocpg_h16::f32x16 f32x16;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BK = 64, NT = 256;
@@ -35,35 +37,58 @@ constexpr int ALD = BK + 8;            // A image [m][k]: 144-byte rows (16-B al
 
 constexpr int DECLINE_SHAPE = -2000, DECLINE_ALIGN = -2001, DECLINE_DTYPE = -2002;
 
-__device__ __forceinline__ void unpack8(const uint4 u, float (&f)[8]) {
-  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+// storage type of a kernel (h16_elem.h) with the packed widening / RNE narrowing of this epilogue: all that differs between the types
+struct Bf16 : ocpg_h16::Bf16 {
+  static __device__ __forceinline__ void unpack8(const uint4 u, float (&f)[8]) {
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = __uint_as_float(w[i] << 16);
-    f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+    for (int i = 0; i < 4; ++i) {
+      f[2 * i] = __uint_as_float(w[i] << 16);
+      f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+    }
   }
-}
-
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-  uint32_t w[4];
+  static __device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
+    uint32_t w[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
-    w[i] = (uint32_t)__bfloat16_as_ushort(__float2bfloat16(f[2 * i])) | ((uint32_t)__bfloat16_as_ushort(__float2bfloat16(f[2 * i + 1])) << 16);
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-struct Epi {
-  const __hip_bfloat16* c;      // may alias out_skip (not __restrict__)
-  const __hip_bfloat16* mask;
-  const float* scale;
-  __hip_bfloat16* out;
-  __hip_bfloat16* out_skip;
+    for (int i = 0; i < 4; ++i)
+      w[i] = (uint32_t)__bfloat16_as_ushort(__float2bfloat16(f[2 * i])) | ((uint32_t)__bfloat16_as_ushort(__float2bfloat16(f[2 * i + 1])) << 16);
+    return make_uint4(w[0], w[1], w[2], w[3]);
+  }
 };
+struct Fp16 : ocpg_h16::Fp16 {
+  static __device__ __forceinline__ void unpack8(const uint4 u, float (&f)[8]) {
+    const __half2* h = reinterpret_cast<const __half2*>(&u);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float2 t = __half22float2(h[i]);
+      f[2 * i] = t.x;
+      f[2 * i + 1] = t.y;
+    }
+  }
+  static __device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
+    uint32_t w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      w[i] = (uint32_t)__half_as_ushort(__float2half_rn(f[2 * i])) | ((uint32_t)__half_as_ushort(__float2half_rn(f[2 * i + 1])) << 16);
+    return make_uint4(w[0], w[1], w[2], w[3]);
+  }
+};
+
+template <typename T>
+struct EpiT {
+  const T* c;      // may alias out_skip (not __restrict__)
+  const T* mask;
+  const float* scale;
+  T* out;
+  T* out_skip;
+};
+using Epi = EpiT<__hip_bfloat16>;
 
 // C and mask of 8 consecutive columns, loaded ahead of the arithmetic (all of a thread's loads in flight at once: the epilogue is the
 // memory-bound part of the short-K sites)
 struct In8 { uint4 c, y; };
-__device__ __forceinline__ In8 load8(const Epi& e, long long off) {
+template <typename T>
+__device__ __forceinline__ In8 load8(const EpiT<T>& e, long long off) {
   In8 r{make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)};
   if (e.c) r.c = *reinterpret_cast<const uint4*>(e.c + off);
   if (e.mask) r.y = *reinterpret_cast<const uint4*>(e.mask + off);
@@ -71,31 +96,33 @@ __device__ __forceinline__ In8 load8(const Epi& e, long long off) {
 }
 
 // 8 consecutive columns col .. col + 7 of one row; off = row * N + col
-__device__ __forceinline__ void epilogue8(const Epi& e, long long off, int col, float (&v)[8], const In8& in) {
+template <typename E>
+__device__ __forceinline__ void epilogue8(const EpiT<typename E::T>& e, long long off, int col, float (&v)[8], const In8& in) {
   if (e.c) {
     float c[8];
-    unpack8(in.c, c);
+    E::unpack8(in.c, c);
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] += c[i];
   }
   if (e.mask) {
     float y[8];
-    unpack8(in.y, y);
+    E::unpack8(in.y, y);
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = y[i] > 0.f ? v[i] : 0.f;           // ocpg_bn_act_bwd's test on the saved output
   }
-  if (e.out_skip) *reinterpret_cast<uint4*>(e.out_skip + off) = pack8(v);
+  if (e.out_skip) *reinterpret_cast<uint4*>(e.out_skip + off) = E::pack8(v);
   if (e.scale) {
     const float4 s0 = reinterpret_cast<const float4*>(e.scale + col)[0], s1 = reinterpret_cast<const float4*>(e.scale + col)[1];
     v[0] *= s0.x, v[1] *= s0.y, v[2] *= s0.z, v[3] *= s0.w, v[4] *= s1.x, v[5] *= s1.y, v[6] *= s1.z, v[7] *= s1.w;
   }
-  *reinterpret_cast<uint4*>(e.out + off) = pack8(v);
+  *reinterpret_cast<uint4*>(e.out + off) = E::pack8(v);
 }
 
 // grid: mtiles * ntiles workgroups (1-D)
-template <int TM, int TN>
-__global__ __launch_bounds__(NT) void gemm_dgrad_bn(const __hip_bfloat16* __restrict__ a, const __hip_bfloat16* __restrict__ w, Epi e,
-                                                    long long M, int N, int K, int mtiles, int ntiles) {
+template <typename E, int TM, int TN>
+__device__ __forceinline__ void gemm_dgrad_bn_body(const typename E::T* __restrict__ a, const typename E::T* __restrict__ w,
+                                                   const EpiT<typename E::T>& e, long long M, int N, int K, int mtiles, int ntiles) {
+  using T = typename E::T;
   constexpr int BLD = TN + 8;          // B image [k][n]: rows 16-B aligned, 4 banks apart
   constexpr int SLD = TN + 4;          // fp32 accumulator image [m][n] for the epilogue
   constexpr int WM = TM / 2, WN = TN / 2, IM = WM / 32, JN = WN / 32;     // wave tile and its 32x32 accumulators
@@ -120,13 +147,13 @@ __global__ __launch_bounds__(NT) void gemm_dgrad_bn(const __hip_bfloat16* __rest
   // staging identity.  A: row arow + 32 i, 16-B segment aseg of the 64-wide K step; rows past M read row M - 1 (never stored).
   // B: k row kr + BROWS i, columns n0 + 8 bseg ..
   const int arow = tid >> 3, aseg = tid & 7, kr = tid / BSEG, bseg = tid % BSEG;
-  const __hip_bfloat16* ap[A_L];
+  const T* ap[A_L];
 #pragma unroll
   for (int i = 0; i < A_L; ++i) {
     const long long r = min(m0 + arow + 32 * i, M - 1);
     ap[i] = a + r * K + aseg * 8;
   }
-  const __hip_bfloat16* wp = w + (long long)kr * N + n0 + bseg * 8;
+  const T* wp = w + (long long)kr * N + n0 + bseg * 8;
   const long long wstep = (long long)BROWS * N;            // B rows between a thread's consecutive loads
 
   // register sets are native vectors: with HIP's uint4 (a class) the two sets lived in scratch
@@ -134,7 +161,7 @@ __global__ __launch_bounds__(NT) void gemm_dgrad_bn(const __hip_bfloat16* __rest
     const int ks = min(s, ksteps - 1);
 #pragma unroll
     for (int i = 0; i < A_L; ++i) Ra[i] = *reinterpret_cast<const u32x4*>(ap[i] + ks * BK);
-    const __hip_bfloat16* wk = wp + (long long)ks * BK * N;
+    const T* wk = wp + (long long)ks * BK * N;
 #pragma unroll
     for (int i = 0; i < B_L; ++i) Rb[i] = *reinterpret_cast<const u32x4*>(wk + i * wstep);
   };
@@ -174,7 +201,7 @@ __global__ __launch_bounds__(NT) void gemm_dgrad_bn(const __hip_bfloat16* __rest
 #pragma unroll
       for (int i = 0; i < IM; ++i)
 #pragma unroll
-        for (int j = 0; j < JN; ++j) acc[i * JN + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bf[j], acc[i * JN + j], 0, 0, 0);
+        for (int j = 0; j < JN; ++j) acc[i * JN + j] = E::mfma(af[i], bf[j], acc[i * JN + j]);
     }
   };
 
@@ -227,8 +254,20 @@ __global__ __launch_bounds__(NT) void gemm_dgrad_bn(const __hip_bfloat16* __rest
     if (grow >= M) continue;
     const float4 x0 = *reinterpret_cast<const float4*>(&st[row * SLD + c8]), x1 = *reinterpret_cast<const float4*>(&st[row * SLD + c8 + 4]);
     float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-    epilogue8(e, grow * N + n0 + c8, n0 + c8, v, in[q]);
+    epilogue8<E>(e, grow * N + n0 + c8, n0 + c8, v, in[q]);
   }
+}
+
+template <int TM, int TN>
+__global__ __launch_bounds__(NT) void gemm_dgrad_bn(const __hip_bfloat16* __restrict__ a, const __hip_bfloat16* __restrict__ w, Epi e,
+                                                    long long M, int N, int K, int mtiles, int ntiles) {
+  gemm_dgrad_bn_body<Bf16, TM, TN>(a, w, e, M, N, K, mtiles, ntiles);
+}
+
+template <int TM, int TN>
+__global__ __launch_bounds__(NT) void gemm_dgrad_bn_f16(const __half* __restrict__ a, const __half* __restrict__ w, EpiT<__half> e,
+                                                        long long M, int N, int K, int mtiles, int ntiles) {
+  gemm_dgrad_bn_body<Fp16, TM, TN>(a, w, e, M, N, K, mtiles, ntiles);
 }
 
 constexpr int TILE_M[3] = {128, 64, 64}, TILE_N[3] = {128, 128, 64};
@@ -248,7 +287,7 @@ extern "C" int ocpg_gemm_dgrad_bn_tile(long long M, int N, int K) {
 
 extern "C" int ocpg_gemm_dgrad_bn(const void* a, const void* w, const void* c, const void* mask, const float* scale, void* out, void* out_skip,
                                   long long M, int N, int K, int dtype, int tile, void* stream) {
-  if (dtype != 1) return DECLINE_DTYPE;
+  if (dtype != 1 && dtype != 2) return DECLINE_DTYPE;
   if (M < 0 || N <= 0 || K <= 0) return -1007;
   if (tile < 0 || tile > 2) return -1011;
   if (N % TILE_N[tile] != 0 || K % (2 * BK) != 0) return DECLINE_SHAPE;
@@ -260,9 +299,18 @@ extern "C" int ocpg_gemm_dgrad_bn(const void* a, const void* w, const void* c, c
     if (p && !aligned16(p)) return DECLINE_ALIGN;
   if (M == 0) return 0;
   const hipStream_t st = (hipStream_t)stream;
-  const Epi e{(const __hip_bfloat16*)c, (const __hip_bfloat16*)mask, scale, (__hip_bfloat16*)out, (__hip_bfloat16*)out_skip};
   const int mtiles = (int)((M + TILE_M[tile] - 1) / TILE_M[tile]), ntiles = N / TILE_N[tile];
   const dim3 grid((unsigned)(mtiles * ntiles)), block(NT);
+  if (dtype == 2) {
+    const EpiT<__half> e{(const __half*)c, (const __half*)mask, scale, (__half*)out, (__half*)out_skip};
+    const __half *ap = (const __half*)a, *wp = (const __half*)w;
+    if (tile == 0) gemm_dgrad_bn_f16<128, 128><<<grid, block, 0, st>>>(ap, wp, e, M, N, K, mtiles, ntiles);
+    else if (tile == 1) gemm_dgrad_bn_f16<64, 128><<<grid, block, 0, st>>>(ap, wp, e, M, N, K, mtiles, ntiles);
+    else gemm_dgrad_bn_f16<64, 64><<<grid, block, 0, st>>>(ap, wp, e, M, N, K, mtiles, ntiles);
+    const hipError_t err = hipGetLastError();
+    return err == hipSuccess ? 0 : -(int)err;
+  }
+  const Epi e{(const __hip_bfloat16*)c, (const __hip_bfloat16*)mask, scale, (__hip_bfloat16*)out, (__hip_bfloat16*)out_skip};
   const __hip_bfloat16 *ap = (const __hip_bfloat16*)a, *wp = (const __hip_bfloat16*)w;
   if (tile == 0) gemm_dgrad_bn<128, 128><<<grid, block, 0, st>>>(ap, wp, e, M, N, K, mtiles, ntiles);
   else if (tile == 1) gemm_dgrad_bn<64, 128><<<grid, block, 0, st>>>(ap, wp, e, M, N, K, mtiles, ntiles);

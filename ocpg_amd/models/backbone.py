@@ -65,7 +65,7 @@ class FrozenBatchNorm2d(nn.Module):
 
 
 FUSED_CONV_BN = os.environ.get("OCPG_FUSED_CONV_BN", "1") != "0"     # A/B switch
-MFMA_CONV3X3 = os.environ.get("OCPG_MFMA_CONV3X3", "1") != "0"     # A/B switch: 3x3 conv + BN + ReLU by csrc/conv3x3_mfma.hip (bf16, >= 128 channels)
+MFMA_CONV3X3 = os.environ.get("OCPG_MFMA_CONV3X3", "1") != "0"     # A/B switch: 3x3 conv + BN + ReLU by csrc/conv3x3_mfma.hip (bf16 / fp16, >= 128 channels)
 STRIDED_1X1 = os.environ.get("OCPG_STRIDED_1X1", "1") != "0"     # A/B switch: the stride-2 projection shortcuts as subsample + GEMM (else MIOpen)
 FUSED_CONV3X3_BN = os.environ.get("OCPG_FUSED_CONV3X3_BN", "0") != "0"     # opt-in: 3x3 conv + BN + ReLU as im2col + epilogue GEMM (small maps); measured neutral in the step
 

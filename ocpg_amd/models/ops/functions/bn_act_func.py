@@ -9,7 +9,7 @@ from torch.autograd.function import once_differentiable
 
 from ...._lib import check, lib, stream_ptr
 
-_DT = {torch.float32: 0, torch.bfloat16: 1}
+_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 
 def _layout(x):

@@ -17,7 +17,8 @@ from torch.autograd.function import once_differentiable
 
 from ...._lib import check, lib
 
-_DT = {torch.float32: 0, torch.bfloat16: 1}
+_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+_H16 = (torch.bfloat16, torch.float16)      # the 16-bit storage types of the own MFMA kernels (fp16: the reference's --amp mode)
 _CL = torch.channels_last
 EPILOGUE = os.environ.get("OCPG_GEMM_EPILOGUE", "1") != "0"     # A/B switch: BN affine / skip / ReLU in the GEMM epilogue
 # A/B switch: the gradient of a bottleneck's identity skip is ADDED BY THE GEMM that computes conv1's input gradient (C = gz W + 1.0 C on
@@ -57,6 +58,12 @@ def _same_tensor(a, b):
 
 def _tensor_key(t):
     return (t.data_ptr(), tuple(t.shape), t.dtype, tuple(t.stride()), t._version)
+
+
+def _both16(*ts):
+    """Every tensor is of ONE 16-bit dtype (an own MFMA kernel reads all its operands as the same storage type: a bf16 tensor must never
+    reach an fp16 instantiation, nor the reverse)."""
+    return ts[0].dtype in _H16 and all(t.dtype == ts[0].dtype for t in ts)
 
 
 def _offer_token(y, scale, skip, switch):
@@ -183,11 +190,11 @@ class Conv1x1BNAct(Function):
         ctx.w_cast = is_cast_copy(w)
         ctx.give = ctx.take = None
         # consumer: x IS a conv + BN + ReLU output whose BN + ReLU backward this node's input-gradient kernel can take over
-        ctx.claim = _claim_token(x) if (FUSED_DGRAD_BN and x.dtype == torch.bfloat16 and ctx.needs_input_grad[0]) else None
+        ctx.claim = _claim_token(x) if (FUSED_DGRAD_BN and _both16(x, w) and ctx.needs_input_grad[0]) else None
         ctx.premask = None          # producer: the token of y
-        if PREMASK and relu and skip is None and x.dtype == torch.bfloat16 and ctx.needs_input_grad[1]:
+        if PREMASK and relu and skip is None and _both16(x, w) and ctx.needs_input_grad[1]:
             ctx.premask = _offer_token(y, scale, False, "OCPG_PREMASK_DGRAD")
-        elif FUSED_DGRAD_BN and relu and skip is not None and x.dtype == torch.bfloat16 and any(ctx.needs_input_grad):
+        elif FUSED_DGRAD_BN and relu and skip is not None and _both16(x, w) and any(ctx.needs_input_grad):
             ctx.premask = _offer_token(y, scale, True, "OCPG_FUSED_DGRAD_BN")
         if SKIP_GRAD_IN_GEMM:
             if skip is not None:
@@ -279,7 +286,7 @@ def conv1x1_bn_act(x, w, scale, shift, skip, relu, splits):
 
 
 # ---- 3x3 conv (padding == dilation, stride 1|2) + frozen BN + ReLU: im2col (HIP) -> GEMM with the BN/ReLU epilogue ---------
-_DT3 = {torch.float32: 0, torch.bfloat16: 1}
+_DT3 = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 
 def eligible3x3(x, conv):
@@ -364,9 +371,11 @@ def conv3x3_bn_act(x, w, scale, shift, relu, stride, dil, splits):
 
 # ---- 3x3 conv (padding 1, stride 1|2) + frozen BN + ReLU on the matrix cores: csrc/conv3x3_mfma.hip ------------------------
 def eligible3x3_mfma(x, conv):
-    """bf16 channels-last map, 3x3 / padding 1 / dilation 1 / stride 1|2 / no bias, channel counts the kernel's K step and its
+    """bf16 or fp16 channels-last map (weight of the same type), 3x3 / padding 1 / dilation 1 / stride 1|2 / no bias, channel counts the kernel's K step and its
     output tile serve (multiples of 64, >= _MFMA_MIN_C: ResNet layers 2-4; the 64-channel layer1 keeps MIOpen, which is faster there)."""
-    return (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16 and conv.kernel_size == (3, 3) and conv.groups == 1
+    if x.dtype == torch.float16 and (BODY_SPLITK or not DGRAD_OWN_WEIGHT):
+        return False        # these A/B switches select kernels that have no fp16 form: the fp16 call keeps the library path, bn(conv(x))
+    return (x.is_cuda and x.dim() == 4 and x.dtype in _H16 and conv.kernel_size == (3, 3) and conv.groups == 1
             and conv.bias is None and conv.stride[0] == conv.stride[1] and conv.stride[0] in (1, 2) and conv.dilation == (1, 1)
             and conv.padding == (1, 1) and conv.padding_mode == "zeros" and x.is_contiguous(memory_format=_CL)
             and x.shape[1] % 64 == 0 and conv.out_channels % 64 == 0 and x.shape[1] >= _MFMA_MIN_C and conv.out_channels >= _MFMA_MIN_C)
@@ -388,6 +397,11 @@ class Conv3x3MfmaBNAct(Function):
         n, c, h, wd = x.shape
         co = w.shape[0]
         ho, wo = (h - 1) // stride + 1, (wd - 1) // stride + 1
+        if not _both16(x, w):
+            raise RuntimeError(f"Conv3x3MfmaBNAct: x and w must share one 16-bit dtype, got {x.dtype} and {w.dtype}")
+        fp16 = x.dtype == torch.float16
+        if fp16 and (BODY_SPLITK or not DGRAD_OWN_WEIGHT):      # eligible3x3_mfma keeps such a call on the library path
+            raise RuntimeError("Conv3x3MfmaBNAct: OCPG_CONV3X3_SPLITK / OCPG_DGRAD_OWN_WEIGHT=0 select kernels that have no fp16 form")
         w2 = w.permute(0, 2, 3, 1)                                   # [co,3,3,c]: a view when the weight is channels-last
         if not w2.is_contiguous():
             w2 = w2.contiguous()
@@ -401,6 +415,10 @@ class Conv3x3MfmaBNAct(Function):
             part = torch.empty((sp, n * ho * wo, co), dtype=torch.float32, device=x.device)
             check(lib().ocpg_conv3x3_mfma_fwd_bn_splitk(x.data_ptr(), w2.data_ptr(), scale.data_ptr(), shift.data_ptr(), int(relu), n, h, wd, c, co, stride,
                                                         sp, part.data_ptr(), y.data_ptr(), st), "ocpg_conv3x3_mfma_fwd_bn_splitk")
+        elif fp16:      # the fp16 instantiation (the bf16 path keeps the un-suffixed symbol: same kernel, same call census as before)
+            check(lib().ocpg_conv3x3_mfma_fwd_cols_h16(x.data_ptr(), w2.data_ptr(), scale.data_ptr(), shift.data_ptr(), int(relu), n, h, wd, c, co,
+                                                       stride, y.data_ptr(), None if cols is None else cols.data_ptr(), 2, st),
+                  "ocpg_conv3x3_mfma_fwd_cols_h16")
         else:
             check(lib().ocpg_conv3x3_mfma_fwd_cols(x.data_ptr(), w2.data_ptr(), scale.data_ptr(), shift.data_ptr(), int(relu), n, h, wd, c, co, stride,
                                                    y.data_ptr(), None if cols is None else cols.data_ptr(), st), "ocpg_conv3x3_mfma_fwd_cols")
@@ -416,7 +434,7 @@ class Conv3x3MfmaBNAct(Function):
         ctx.premask = tok if (tok is not None and not tok["skip"] and ctx.needs_input_grad[0]) else None
         # producer (site a): y's one consumer, the bottleneck's conv3, may apply this BN + ReLU backward in its input-gradient kernel
         ctx.offer = (_offer_token(y, scale, False, "OCPG_FUSED_DGRAD_BN")
-                     if (FUSED_DGRAD_BN and relu and x.dtype == torch.bfloat16 and any(ctx.needs_input_grad)) else None)
+                     if (FUSED_DGRAD_BN and relu and any(ctx.needs_input_grad)) else None)
         return y
 
     @staticmethod
@@ -427,6 +445,8 @@ class Conv3x3MfmaBNAct(Function):
         n, c, h, wd = x.shape
         co, ho, wo = y.shape[1], y.shape[2], y.shape[3]
         m, k = n * ho * wo, 9 * c
+        dt = _DT[y.dtype]                   # 1 bf16 / 2 fp16: every operand below is of y's type
+        fp16 = dt == 2
         L = lib()
         st = torch.cuda.current_stream().cuda_stream
         if gy.dtype != y.dtype or not gy.is_contiguous(memory_format=_CL):
@@ -436,14 +456,17 @@ class Conv3x3MfmaBNAct(Function):
             gz = gy
         else:
             gz = torch.empty_like(y)
-            check(L.ocpg_bn_act_bwd(gy.data_ptr(), y.data_ptr(), scale.data_ptr(), gz.data_ptr(), None, m, co, 1, int(relu), 1, st), "ocpg_bn_act_bwd")
+            check(L.ocpg_bn_act_bwd(gy.data_ptr(), y.data_ptr(), scale.data_ptr(), gz.data_ptr(), None, m, co, 1, int(relu), dt, st), "ocpg_bn_act_bwd")
         gx = gw = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty((n, c, h, wd), dtype=y.dtype, device=y.device, memory_format=_CL)
             tok = ctx.premask       # x IS the layer in front's bn + ReLU output: its backward rides in this kernel's epilogue
             mask_ptr, scale_ptr = (x.data_ptr(), tok["scale"].data_ptr()) if tok is not None else (None, None)
-            sp = int(L.ocpg_conv3x3_mfma_body_splits(n * h * wd, c, co)) if (BODY_SPLITK and DGRAD_OWN_WEIGHT and c % 8 == 0) else 1
-            if sp > 1:
+            sp = int(L.ocpg_conv3x3_mfma_body_splits(n * h * wd, c, co)) if (BODY_SPLITK and DGRAD_OWN_WEIGHT and c % 8 == 0 and not fp16) else 1
+            if fp16:        # the forward admitted fp16 only with the own-weight kernel selected; its fp16 instantiation
+                check(L.ocpg_conv3x3_mfma_dgrad_w_h16(gz.data_ptr(), w2.data_ptr(), mask_ptr, scale_ptr, n, h, wd, c, co, stride, gx.data_ptr(), 2, st),
+                      "ocpg_conv3x3_mfma_dgrad_w_h16")
+            elif sp > 1:
                 part = torch.empty((sp, n * h * wd, c), dtype=torch.float32, device=y.device)
                 check(L.ocpg_conv3x3_mfma_dgrad_w_splitk(gz.data_ptr(), w2.data_ptr(), mask_ptr, scale_ptr, n, h, wd, c, co, stride, sp, part.data_ptr(),
                                                          gx.data_ptr(), st), "ocpg_conv3x3_mfma_dgrad_w_splitk")
@@ -464,23 +487,27 @@ class Conv3x3MfmaBNAct(Function):
                     # straight from the two maps (csrc/conv3x3_wgrad.hip): no patch matrix, no library GEMM
                     sp = int(L.ocpg_conv3x3_mfma_wgrad_splits(n, h, wd, c, co, stride))
                     part = torch.empty((sp, co, k), dtype=y.dtype, device=y.device)
-                    check(L.ocpg_conv3x3_mfma_wgrad(gz.data_ptr(), x.data_ptr(), n, h, wd, c, co, stride, part.data_ptr(), st), "ocpg_conv3x3_mfma_wgrad")
+                    if fp16:
+                        check(L.ocpg_conv3x3_mfma_wgrad_h16(gz.data_ptr(), x.data_ptr(), n, h, wd, c, co, stride, part.data_ptr(), 2, st),
+                              "ocpg_conv3x3_mfma_wgrad_h16")
+                    else:
+                        check(L.ocpg_conv3x3_mfma_wgrad(gz.data_ptr(), x.data_ptr(), n, h, wd, c, co, stride, part.data_ptr(), st), "ocpg_conv3x3_mfma_wgrad")
                     g2 = _reduce_partials(part, ctx.w_cast) if sp > 1 else part[0]
                 else:
                     if ctx.has_cols:
                         cols = ctx.saved_tensors[4]
                     else:
                         cols = torch.empty((m, k), dtype=y.dtype, device=y.device)
-                        check(L.ocpg_im2col3x3_nhwc(x.data_ptr(), n, h, wd, c, stride, 1, cols.data_ptr(), 1, st), "ocpg_im2col3x3_nhwc")
+                        check(L.ocpg_im2col3x3_nhwc(x.data_ptr(), n, h, wd, c, stride, 1, cols.data_ptr(), dt, st), "ocpg_im2col3x3_nhwc")
                     if splits > 1 and m % splits == 0:
                         r = m // splits
                         part = torch.empty((splits, co, k), dtype=y.dtype, device=y.device)
-                        check(L.ocpg_gemm(gz.data_ptr(), cols.data_ptr(), part.data_ptr(), None, 1, 1, 1, 0, co, k, r, co, k, k, splits, r * co, r * k,
+                        check(L.ocpg_gemm(gz.data_ptr(), cols.data_ptr(), part.data_ptr(), None, dt, dt, 1, 0, co, k, r, co, k, k, splits, r * co, r * k,
                                           co * k, 1.0, 0.0, st), "ocpg_gemm")
                         g2 = _reduce_partials(part, ctx.w_cast)
                     else:
                         g2 = torch.empty((co, k), dtype=y.dtype, device=y.device)
-                        check(L.ocpg_gemm(gz.data_ptr(), cols.data_ptr(), g2.data_ptr(), None, 1, 1, 1, 0, co, k, m, co, k, k, 1, 0, 0, 0, 1.0, 0.0, st),
+                        check(L.ocpg_gemm(gz.data_ptr(), cols.data_ptr(), g2.data_ptr(), None, dt, dt, 1, 0, co, k, m, co, k, k, 1, 0, 0, 0, 1.0, 0.0, st),
                               "ocpg_gemm")
                 gw = sw.publish(g2).view(co, 3, 3, c).permute(0, 3, 1, 2)          # channels-last strides of [co, c, 3, 3]
         return gx, gw, None, None, None, None, None

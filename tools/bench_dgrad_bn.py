@@ -4,7 +4,11 @@ around the C-ABI calls, median of 30; BN_COLD=1 writes 1 GiB between calls.  One
 tile ocpg_gemm_dgrad_bn_tile picks (and at every other tile, "by_tile"), TFLOP/s against 2.5 PF, GB/s of the fused kernel's byte floor
 against 8 TB/s, and which bound is the larger.
 Site (a): conv3's input gradient, out = bf16(v [x > 0] scale2);  site (b): conv1's, C = the parked skip gradient, out_skip = bf16(m),
-out = bf16(m scale3), m = (v + C) [x > 0]."""
+out = bf16(m scale3), m = (v + C) [x > 0].
+--dtype bf16 (default) | fp16 | both: the storage type (C-ABI dtype code 1 / 2).  `both` times every shape as bf16, fp16, bf16 in that
+order ("rep" 0 / 1 in the line): the two bf16 figures of one call are the run-to-run spread the fp16 figure is read against."""
+import argparse
+import itertools
 import json
 import os
 import sys
@@ -19,6 +23,11 @@ SITES = (("a", "L2", 38400, 128, 512), ("a", "L3", 9600, 256, 1024), ("a", "L4",
 dev = torch.device("cuda:0")
 cold_buf = torch.empty(1 << 28, dtype=torch.float32, device=dev) if os.environ.get("BN_COLD") == "1" else None
 L = lib()
+ap = argparse.ArgumentParser()
+ap.add_argument("--dtype", choices=("bf16", "fp16", "both"), default="bf16")
+ARGS = ap.parse_args()
+RUNS = {"bf16": (("bf16", 0),), "fp16": (("fp16", 0),), "both": (("bf16", 0), ("fp16", 0), ("bf16", 1))}[ARGS.dtype]
+TORCH_DT = {"bf16": (torch.bfloat16, 1), "fp16": (torch.float16, 2)}
 
 
 def timed(fn, n=30):
@@ -32,28 +41,29 @@ def timed(fn, n=30):
 
 
 for site, layer, m2, n, k in SITES:
-    for clips in (2, 1):
+    for clips, (dname, rep_i) in itertools.product((2, 1), RUNS):
+        tdt, code = TORCH_DT[dname]
         m = m2 * clips // 2
         g = torch.Generator().manual_seed(0)
-        a = torch.randn(m, k, generator=g).to(dev, torch.bfloat16)                 # gz of the consumer
-        w = (torch.randn(k, n, generator=g) / k ** 0.5).to(dev, torch.bfloat16)    # its weight [Cout][Cin]
-        x = torch.randn(m, n, generator=g).to(dev, torch.bfloat16)                 # its input = the mask
+        a = torch.randn(m, k, generator=g).to(dev, tdt)                 # gz of the consumer
+        w = (torch.randn(k, n, generator=g) / k ** 0.5).to(dev, tdt)    # its weight [Cout][Cin]
+        x = torch.randn(m, n, generator=g).to(dev, tdt)                 # its input = the mask
         scale = (torch.rand(n, generator=g) + 0.5).to(dev)
-        c = torch.randn(m, n, generator=g).to(dev, torch.bfloat16) if site == "b" else None
-        gx, gz, gskip = (torch.empty(m, n, dtype=torch.bfloat16, device=dev) for _ in range(3))
+        c = torch.randn(m, n, generator=g).to(dev, tdt) if site == "b" else None
+        gx, gz, gskip = (torch.empty(m, n, dtype=tdt, device=dev) for _ in range(3))
         tile = int(L.ocpg_gemm_dgrad_bn_tile(m, n, k))
         st = stream_ptr()
 
         def old():          # what conv_bn_func ran before: hipBLASLt dgrad (beta = 1 onto C at site b), then the BN / ReLU backward
             dst = c if c is not None else gx
-            assert L.ocpg_gemm(a.data_ptr(), w.data_ptr(), dst.data_ptr(), None, 1, 1, 0, 0, m, n, k, k, n, n, 1, 0, 0, 0, 1.0,
+            assert L.ocpg_gemm(a.data_ptr(), w.data_ptr(), dst.data_ptr(), None, code, code, 0, 0, m, n, k, k, n, n, 1, 0, 0, 0, 1.0,
                                1.0 if c is not None else 0.0, st) == 0
             assert L.ocpg_bn_act_bwd(dst.data_ptr(), x.data_ptr(), scale.data_ptr(), gz.data_ptr(), gskip.data_ptr() if c is not None else None,
-                                     m, n, 1, 1, 1, st) == 0
+                                     m, n, 1, 1, code, st) == 0
 
         def new(t=tile):
             assert L.ocpg_gemm_dgrad_bn(a.data_ptr(), w.data_ptr(), None if c is None else c.data_ptr(), x.data_ptr(), scale.data_ptr(),
-                                        gz.data_ptr(), None if c is None else c.data_ptr(), m, n, k, 1, t, st) == 0
+                                        gz.data_ptr(), None if c is None else c.data_ptr(), m, n, k, code, t, st) == 0
 
         # the fused result against the pair on the same inputs (C is updated in place by both: compare from a fresh copy)
         c0 = None if c is None else c.clone()
@@ -69,7 +79,7 @@ for site, layer, m2, n, k in SITES:
         flops = 2.0 * m * n * k
         byt = 2.0 * (m * k + k * n + m * n * (2 if c is None else 4))           # A + W + mask (+ C) + outputs
         t_floor = max(flops / PEAK_FLOPS, byt / PEAK_BW) * 1e6
-        print(json.dumps({"site": site, "layer": layer, "clips": clips, "M": m, "N": n, "K": k, "tile": ("128x128", "64x128", "64x64")[tile],
+        print(json.dumps({"dtype": dname, "rep": rep_i, "site": site, "layer": layer, "clips": clips, "M": m, "N": n, "K": k, "tile": ("128x128", "64x128", "64x64")[tile],
                           "cold": cold_buf is not None, "old_pair_us": round(t_old, 1), "fused_us": round(t_new, 1),
                           "speedup": round(t_old / t_new, 2), "fused_TFLOPs": round(flops / t_new / 1e6, 1),
                           "frac_of_2.5PF": round(flops / t_new / 1e6 / 2500, 3), "fused_GBs": round(byt / t_new / 1e3, 1),

@@ -1,65 +1,20 @@
-"""Kernel resource usage (registers, scratch, occupancy, static LDS) of every MSDeformAttn kernel, from the compiler's own remarks
-(hipcc -Rpass-analysis=kernel-resource-usage; needs no GPU).  One line per kernel, sorted by name, so that two listings diff cleanly:
+"""Kernel resource usage of every MSDeformAttn kernel: tools/kernel_resource_usage.py with the pattern 'msda*.hip' (the old name, kept):
 
     python tools/msda_resource_usage.py > profiles/msda_resource_usage.txt
 
+With arguments: saved remark files to parse instead of compiling, as before.
 The fp32 kernels' lines must not move when a kernel next to them is added or templated."""
-import glob
 import os
-import re
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from ocpg_amd.csrc import build  # noqa: E402
-
-FIELDS = ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]")
-
-
-def parse(text):
-    """remarks of one compile -> {demangled kernel name: {field: value}}"""
-    out, cur = {}, None
-    for line in text.splitlines():
-        m = re.search(r"remark: (?:.*?)Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        if cur is None:
-            continue
-        for f in FIELDS:
-            m = re.search(r"remark:\s+" + re.escape(f) + r": (\d+)", line)
-            if m:
-                cur[f] = int(m.group(1))
-    if not out:
-        return {}
-    names = list(out)
-    dem = subprocess.run(["c++filt"] + names, capture_output=True, text=True, check=True).stdout.splitlines()
-    return {d.replace("(anonymous namespace)::", "").replace("void ", "", 1).split("(")[0]: out[n] for n, d in zip(names, dem)}
-
-
-def listing(kernels):
-    rows = []
-    for name in sorted(kernels):
-        k = kernels[name]
-        rows.append("%-78s sgpr %3d  vgpr %3d  agpr %3d  scratch %4d  occupancy %d  lds %6d" % (
-            name, k.get("TotalSGPRs", -1), k.get("VGPRs", -1), k.get("AGPRs", -1), k.get("ScratchSize [bytes/lane]", -1),
-            k.get("Occupancy [waves/SIMD]", -1), k.get("LDS Size [bytes/block]", -1)))
-    return "\n".join(rows)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_resource_usage import FIELDS, listing, parse  # noqa: E402,F401
+import kernel_resource_usage  # noqa: E402
 
 
 def main():
-    if len(sys.argv) > 1:          # parse saved remark files instead of compiling
-        kernels = {}
-        for p in sys.argv[1:]:
-            kernels.update(parse(open(p).read()))
-        print(listing(kernels))
-        return
-    kernels = {}
-    for src in sorted(glob.glob(os.path.join(build.HERE, "msda*.hip"))):
-        cmd = [build.HIPCC] + build.CFLAGS + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.devnull]
-        kernels.update(parse(subprocess.run(cmd, capture_output=True, text=True, check=True).stderr))
-    print(listing(kernels))
+    args = sys.argv[1:]
+    kernel_resource_usage.main((["--remarks"] + args) if args else [], default_patterns=("msda*.hip",))
 
 
 if __name__ == "__main__":
