@@ -226,6 +226,18 @@ int ocpg_win_attn_bwd_mfma(const void* qkv, const float* bias, const float* bias
                            int H, int head_dim, const void* out, const void* dout, const float* lse, void* dqkv, float* Dbuf, void* dS,
                            int dtype, void* stream);
 
+/* Opt-in variant of ocpg_win_attn_bwd_mfma that returns the gradient of the relative-position TABLE [T, H] and writes no dS: the bias
+ * is table[idx[q, key]] with idx[q, key] = tok_code[q] - tok_code[key] + code_off (tok_code [N] int32; the caller guarantees [0, T)).  Each
+ * (window, head) sums its dS (fp32, un-rounded) into T floats of LDS and stores them to partials [BW, H, T] (fp32 workspace); a second
+ * kernel sums over the windows in a fixed order into dtable [T, H].  Both are fully written, rows no pair addresses as exact zeros:
+ * nothing to zero beforehand, no global atomics.  ocpg_win_attn_dtable_supported: 1 when N / head_dim / dtype / T are served (the LDS
+ * holds K, V, the N codes and the T floats) and OCPG_WIN_ATTN_MFMA is not 0, else 0; launches nothing.  The backward returns -2000 in
+ * exactly the cases where that answer is 0, before anything is launched. */
+int ocpg_win_attn_dtable_supported(int N, int head_dim, int dtype, int T);
+int ocpg_win_attn_bwd_mfma_dtable(const void* qkv, const float* bias, const float* biasT, const int* region, float scale, int BW, int NW,
+                                  int N, int H, int head_dim, const void* out, const void* dout, const float* lse, void* dqkv, float* Dbuf,
+                                  const int* tok_code, int code_off, int T, float* partials, float* dtable, int dtype, void* stream);
+
 /* Dynamic (per-query) mask head, forward -- replaces OCPG.dynamic_mask_with_coords + mask_heads_forward
  * (models/ocpg.py:475-549) for the reference's fixed head shape (2 layers, 16 channels, relative coordinates on).
  * Q counts the parameter sets per frame: the reference calls the head once per decoder layer on the SAME mask features

@@ -367,4 +367,33 @@ int ocpg_win_attn_bwd_mfma(const void* qkv, const float* bias, const float* bias
   return ocpg_win_mfma::bwd(qkv, bias, biasT, region, scale, BW, NW, N, H, out, dout, lse, dqkv, Dbuf, dS, dtype, (hipStream_t)stream);
 }
 
+/* Opt-in matrix-core backward that returns the relative-position TABLE gradient (csrc/win_attn_mfma.hip, DTABLE): no dS tensor.  The
+ * table row of (q, key) is tok_code[q] - tok_code[key] + code_off and lies in [0, T) (the caller's guarantee).  partials [BW, H, T] is a
+ * workspace, dtable [T, H] the result; both are fully written.  -2000 as ocpg_win_attn_bwd_mfma, before anything is launched. */
+int ocpg_win_attn_dtable_supported(int N, int head_dim, int dtype, int T) {
+  return mfma_enabled() && N > 0 && ocpg_win_mfma::supported_dtable(N, head_dim, dtype, T) ? 1 : 0;
+}
+
+int ocpg_win_attn_bwd_mfma_dtable(const void* qkv, const float* bias, const float* biasT, const int* region, float scale, int BW, int NW,
+                                  int N, int H, int head_dim, const void* out, const void* dout, const float* lse, void* dqkv, float* Dbuf,
+                                  const int* tok_code, int code_off, int T, float* partials, float* dtable, int dtype, void* stream) {
+  if (int e = check_dims(BW, NW, N, H, head_dim)) return e;
+  if (!mfma_enabled() || !ocpg_win_mfma::supported_dtable(N, head_dim, dtype, T)) return -2000;
+  if (!dtable) return -1020;
+  if (BW == 0)          // no window: the table gradient is still fully written
+    return -(int)hipMemsetAsync(dtable, 0, (size_t)T * H * sizeof(float), (hipStream_t)stream);
+  if (!qkv) return -1001;
+  if (!bias) return -1002;
+  if (!biasT) return -1003;
+  if (!out) return -1011;
+  if (!dout) return -1012;
+  if (!lse) return -1013;
+  if (!dqkv) return -1014;
+  if (!Dbuf) return -1015;
+  if (!tok_code) return -1016;
+  if (!partials) return -1019;
+  return ocpg_win_mfma::bwd_dtable(qkv, bias, biasT, region, scale, BW, NW, N, H, out, dout, lse, dqkv, Dbuf, tok_code, code_off, T, partials,
+                                   dtable, dtype, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -13,4 +13,12 @@ int fwd(const void* qkv, const float* biasT, const int* region, float scale, int
 int bwd(const void* qkv, const float* bias, const float* biasT, const int* region, float scale, int BW, int NW, int N, int H, const void* out,
         const void* dout, const float* lse, void* dqkv, float* Dbuf, void* dS, int dtype, hipStream_t st);
 
+// Opt-in variant: the relative-position TABLE gradient instead of dS.  Table row of (q, key) = tok_code[q] - tok_code[key] + code_off, in
+// [0, T); partials [BW, H, T] fp32 workspace and dtable [T, H] fp32 are fully written (nothing to zero).  supported_dtable: the LDS also
+// holds the N codes and the T floats.
+bool supported_dtable(int N, int head_dim, int dtype, int T);
+int bwd_dtable(const void* qkv, const float* bias, const float* biasT, const int* region, float scale, int BW, int NW, int N, int H,
+               const void* out, const void* dout, const float* lse, void* dqkv, float* Dbuf, const int* tok_code, int code_off, int T,
+               float* partials, float* dtable, int dtype, hipStream_t st);
+
 }  // namespace ocpg_win_mfma

@@ -227,21 +227,33 @@ __global__ __launch_bounds__(256) void k_fwd(const T* __restrict__ qkv, const fl
 //   dq^T[d, q] = scale * sum_key K^T[d, key] dS^T[key, q]      (A = K^T read transposed from the row-major K tile, B = the lane's own dS registers)
 //   dS^T is also written (storage dtype, [BW, H, N(key), N(q)]) for the bias gradient: summing that tensor over the windows costs
 //   2 x 232 MB of streaming traffic at Swin-T stage 1, the per-element float atomics of the vector-ALU kernel 464 MB of atomic adds.
-template <typename T>
-__global__ __launch_bounds__(256) void k_bwd_q(const T* __restrict__ qkv, const float* __restrict__ biasT, const int* __restrict__ region,
-                                               float scale, int NW, int N, int Np, int H, const T* __restrict__ out,
-                                               const T* __restrict__ dout, const float* __restrict__ lse, T* __restrict__ dqkv,
-                                               float* __restrict__ Dbuf, T* __restrict__ dS) {
+//
+// DTABLE (opt-in, ocpg_win_attn_bwd_mfma_dtable): the relative-position bias is a gather from a [T, H] table whose row index is
+// linear in a per-token code, idx[q, key] = code[q] - code[key] + off.  Instead of storing dS^T the workgroup keeps this head's T
+// table-gradient floats in LDS, adds the UN-ROUNDED fp32 dS there (ds_add_f32; consecutive lanes = consecutive q of one key = distinct
+// rows) and stores them to partials[bw, hh, :] at the end: no N x N tensor, no global atomics, nothing to zero beforehand.
+template <typename T, bool DTABLE>
+__device__ __forceinline__ void bwd_q_body(const T* __restrict__ qkv, const float* __restrict__ biasT, const int* __restrict__ region,
+                                           float scale, int NW, int N, int Np, int H, const T* __restrict__ out,
+                                           const T* __restrict__ dout, const float* __restrict__ lse, T* __restrict__ dqkv,
+                                           float* __restrict__ Dbuf, T* __restrict__ dS, const int* __restrict__ tok_code, int code_off,
+                                           int TR, float* __restrict__ partials) {
   typedef MM<T> M;
   typedef decltype(M::bits(0.f)) E;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   E* Ks = reinterpret_cast<E*>(smem);                       // [Np][KROW] (row reads for S^T, transposed reads for dq^T)
   E* Vs = Ks + (size_t)Np * KROW;                           // [Np][KROW]
   int* reg_s = reinterpret_cast<int*>(Vs + (size_t)Np * KROW);
+  int* code_s = reg_s + Np;                                 // DTABLE: [Np] token codes
+  float* tab = reinterpret_cast<float*>(code_s + Np);       // DTABLE: [TR] this (window, head)'s table gradient
   const int bw = blockIdx.x / H, hh = blockIdx.x % H;
   const T* base = qkv + (long long)bw * N * 3 * H * HD;
   stage_rows<T, E>(Ks, base, N, Np, H, hh, 1, 1.f);
   stage_rows<T, E>(Vs, base, N, Np, H, hh, 2, 1.f);
+  if constexpr (DTABLE) {
+    for (int j = threadIdx.x; j < Np; j += blockDim.x) code_s[j] = j < N ? tok_code[j] : 0;      // (padding keys never add)
+    for (int t = threadIdx.x; t < TR; t += blockDim.x) tab[t] = 0.f;
+  }
   const bool shifted = stage_regions(reg_s, region ? region + (long long)(bw % NW) * N : nullptr, N, Np);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
   const float* bT = biasT + (long long)hh * N * N;
@@ -268,6 +280,8 @@ __global__ __launch_bounds__(256) void k_bwd_q(const T* __restrict__ qkv, const 
     Dq += xhalf(Dq);
     const float lqL = lse[((long long)bw * H + hh) * N + qc] * kLog2e;
     const int rq = reg_s[qc];
+    int cq = 0;
+    if constexpr (DTABLE) cq = code_s[qc] + code_off;
     f32x16 dq;
 #pragma unroll
     for (int i = 0; i < 16; ++i) dq[i] = 0.f;
@@ -309,7 +323,12 @@ __global__ __launch_bounds__(256) void k_bwd_q(const T* __restrict__ qkv, const 
         const float ds = p * (dp[i] - Dq);
         const E dsb = M::bits(ds);
         df[i >> 3][i & 7] = dsb;
-        if (dSw && qok && (!tail || key < N)) dSw[(long long)key * N + q] = dsb;       // lanes = consecutive q: 64 contiguous bytes per key
+        if constexpr (DTABLE) {
+          const int ix = cq - code_s[key];                 // the caller guarantees [0, TR); the compare keeps a wrong code inside the LDS table
+          if (qok && (!tail || key < N) && (unsigned)ix < (unsigned)TR) atomicAdd(tab + ix, ds);
+        } else {
+          if (dSw && qok && (!tail || key < N)) dSw[(long long)key * N + q] = dsb;       // lanes = consecutive q: 64 contiguous bytes per key
+        }
       }
 #pragma unroll
       for (int s = 0; s < 2; ++s) dq = M::mfma(tr_frag<T, E>(Ks, kt, s, lane), df[s], dq);
@@ -325,6 +344,56 @@ __global__ __launch_bounds__(256) void k_bwd_q(const T* __restrict__ qkv, const 
       }
       if (h == 0) Dbuf[((long long)bw * H + hh) * N + q] = Dq;
     }
+  }
+  if constexpr (DTABLE) {
+    __syncthreads();
+    float* pw = partials + ((long long)bw * H + hh) * TR;
+    for (int t = threadIdx.x; t < TR; t += blockDim.x) pw[t] = tab[t];
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_bwd_q(const T* __restrict__ qkv, const float* __restrict__ biasT, const int* __restrict__ region,
+                                               float scale, int NW, int N, int Np, int H, const T* __restrict__ out,
+                                               const T* __restrict__ dout, const float* __restrict__ lse, T* __restrict__ dqkv,
+                                               float* __restrict__ Dbuf, T* __restrict__ dS) {
+  bwd_q_body<T, false>(qkv, biasT, region, scale, NW, N, Np, H, out, dout, lse, dqkv, Dbuf, dS, nullptr, 0, 0, nullptr);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_bwd_q_dtable(const T* __restrict__ qkv, const float* __restrict__ biasT,
+                                                      const int* __restrict__ region, float scale, int NW, int N, int Np, int H,
+                                                      const T* __restrict__ out, const T* __restrict__ dout, const float* __restrict__ lse,
+                                                      T* __restrict__ dqkv, float* __restrict__ Dbuf, const int* __restrict__ tok_code,
+                                                      int code_off, int TR, float* __restrict__ partials) {
+  bwd_q_body<T, true>(qkv, biasT, region, scale, NW, N, Np, H, out, dout, lse, dqkv, Dbuf, nullptr, tok_code, code_off, TR, partials);
+}
+
+// dtable[t, h] = sum over the windows of partials[bw, h, t], in an order that depends on nothing but BW: slice s adds bw = s, s + 16, ...
+// ascending, then the 16 slices are added ascending.  Every (t, h) is written, also the rows no (q, key) pair of this N addresses.
+constexpr int RED_S = 16;
+__global__ __launch_bounds__(64 * RED_S) void k_dtable_reduce(const float* __restrict__ partials, int BW, int H, int TR,
+                                                             float* __restrict__ dtable) {
+  __shared__ float part[RED_S][64];
+  const int tx = threadIdx.x & 63, s = threadIdx.x >> 6, hh = blockIdx.y, t = blockIdx.x * 64 + tx;
+  float acc = 0.f;
+  if (t < TR) {
+    const float* p = partials + (long long)hh * TR + t;
+    const long long ld = (long long)H * TR;
+    int bw = s;
+    for (; bw + 3 * RED_S < BW; bw += 4 * RED_S) {           // four loads in flight, added in bw order
+      const float a = p[bw * ld], b = p[(bw + RED_S) * ld], c = p[(bw + 2 * RED_S) * ld], d = p[(bw + 3 * RED_S) * ld];
+      acc += a; acc += b; acc += c; acc += d;
+    }
+    for (; bw < BW; bw += RED_S) acc += p[bw * ld];
+  }
+  part[s][tx] = acc;
+  __syncthreads();
+  if (s == 0 && t < TR) {
+    float v = part[0][tx];
+#pragma unroll
+    for (int k = 1; k < RED_S; ++k) v += part[k][tx];
+    dtable[(long long)t * H + hh] = v;
   }
 }
 
@@ -467,9 +536,48 @@ int bwd_t(const void* qkv, const float* bias, const float* biasT, const int* reg
   return status();
 }
 
+inline size_t bwd_q_dtable_lds(int Np, int TR, size_t esz) { return bwd_q_lds(Np, esz) + (size_t)Np * sizeof(int) + (size_t)TR * sizeof(float); }
+
+template <typename T>
+int bwd_dtable_t(const void* qkv, const float* bias, const float* biasT, const int* region, float scale, int BW, int NW, int N, int H,
+                 const void* out, const void* dout, const float* lse, void* dqkv, float* Dbuf, const int* tok_code, int code_off, int TR,
+                 float* partials, float* dtable, hipStream_t st) {
+  const int Np = (N + 31) / 32 * 32;
+  const size_t l1 = bwd_q_dtable_lds(Np, TR, 2), l2 = bwd_kv_lds(Np, 2);
+  if (l1 > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_bwd_q_dtable<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l1);
+    if (e != hipSuccess) return -(int)e;
+  }
+  if (l2 > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_bwd_kv<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
+    if (e != hipSuccess) return -(int)e;
+  }
+  k_bwd_q_dtable<T><<<BW * H, 256, l1, st>>>((const T*)qkv, biasT, region, scale, NW, N, Np, H, (const T*)out, (const T*)dout, lse, (T*)dqkv,
+                                             Dbuf, tok_code, code_off, TR, partials);
+  if (int e = status()) return e;
+  k_dtable_reduce<<<dim3((TR + 63) / 64, H), 64 * RED_S, 0, st>>>(partials, BW, H, TR, dtable);
+  if (int e = status()) return e;
+  k_bwd_kv<T><<<BW * H, 256, l2, st>>>((const T*)qkv, bias, region, scale, NW, N, Np, H, (const T*)dout, lse, Dbuf, (T*)dqkv);
+  return status();
+}
+
 }  // namespace
 
 namespace ocpg_win_mfma {
+
+bool supported_dtable(int N, int head_dim, int dtype, int T) {
+  if (!supported(N, head_dim, dtype) || T < 1) return false;
+  return bwd_q_dtable_lds((N + 31) / 32 * 32, T, 2) <= 150 * 1024;
+}
+
+int bwd_dtable(const void* qkv, const float* bias, const float* biasT, const int* region, float scale, int BW, int NW, int N, int H,
+               const void* out, const void* dout, const float* lse, void* dqkv, float* Dbuf, const int* tok_code, int code_off, int T,
+               float* partials, float* dtable, int dtype, hipStream_t st) {
+  return dtype == 1 ? bwd_dtable_t<__hip_bfloat16>(qkv, bias, biasT, region, scale, BW, NW, N, H, out, dout, lse, dqkv, Dbuf, tok_code,
+                                                   code_off, T, partials, dtable, st)
+                    : bwd_dtable_t<__half>(qkv, bias, biasT, region, scale, BW, NW, N, H, out, dout, lse, dqkv, Dbuf, tok_code, code_off, T,
+                                           partials, dtable, st);
+}
 
 bool supported(int N, int head_dim, int dtype) {
   if (head_dim != HD || (dtype != 1 && dtype != 2) || N < 1) return false;

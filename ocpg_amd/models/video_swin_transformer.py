@@ -24,9 +24,10 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import amp_cache, fallbacks
+from .. import _lib
 
 from ..util.misc import NestedTensor, mask_key, resize_mask
-from .ops.functions.win_attn_func import window_attention
+from .ops.functions.win_attn_func import table_codes, window_attention, window_attention_table
 from .ops.functions.layernorm_func import LayerNorm as _FusedLayerNorm, PermuteGather, RelPosBias, StaticGather, permute_gather_ok
 from .position_encoding import build_position_encoding
 
@@ -131,6 +132,7 @@ def _lp_norm(norm_layer, dim):
 
 _FUSED_LN = os.environ.get("OCPG_FUSED_SWIN_LN", "1") != "0"
 _RELPOS_KERNEL = os.environ.get("OCPG_RELPOS_KERNEL", "1") != "0"     # A/B switch: relative-position bias (both layouts) from the table in one launch
+_FUSED_DTABLE = os.environ.get("OCPG_WIN_ATTN_FUSED_DTABLE") == "1"   # opt-in: 16-bit attention backward returns the table gradient itself (no dS tensor)
 
 
 class WindowAttention3D(nn.Module):
@@ -174,15 +176,33 @@ class WindowAttention3D(nn.Module):
             return StaticGather.apply(table, idx, plan[1]).view(n, n, -1).permute(2, 0, 1)
         return table[idx].view(n, n, -1).permute(2, 0, 1)
 
+    def _fused_dtable_codes(self, qkv, n):
+        """The token codes of window_attention_table when that path serves this call (16-bit qkv, fp32 table, shape within the kernel's
+        LDS, index linear in the codes), else None: decided before anything is launched."""
+        table = self.relative_position_bias_table
+        if qkv.dtype not in (torch.bfloat16, torch.float16) or table.dtype != torch.float32 or not table.is_contiguous():
+            return None
+        if _lib.lib().ocpg_win_attn_dtable_supported(n, 32, 1 if qkv.dtype == torch.bfloat16 else 2, table.shape[0]) != 1:
+            return None
+        return table_codes(self.relative_position_index[:n, :n], self.__dict__.setdefault("_table_codes", {}))
+
     def forward(self, x, mask=None, region=None):
         """x [num_windows*B, N, C]; mask [num_windows, N, N] additive (0 / -100) or None; region [num_windows, N] int32 =
         the same shift mask as region ids (what the fused HIP kernel consumes instead of the N x N tensor)."""
         bw, n, c = x.shape
         h = self.num_heads
         qkv = self.qkv(x)
+        fused = (x.is_cuda and c // h == 32 and (self.attn_drop.p == 0.0 or not self.training) and (mask is None or region is not None)
+                 and not _GENERIC_ATTENTION)
+        if fused and _FUSED_DTABLE:
+            codes = self._fused_dtable_codes(qkv, n)
+            if codes is not None:             # csrc/win_attn_mfma.hip, DTABLE: the backward hands the table gradient back, no dS tensor
+                nw = region.shape[0] if region is not None else 1
+                out = window_attention_table(qkv.view(bw, n, 3, h, c // h), self.relative_position_bias_table,
+                                             self.relative_position_index[:n, :n], region, self.scale, nw, codes)
+                return self.proj_drop(self.proj(out))
         bias = self.relative_position_bias(n)                                            # [h, N, N]
-        if (x.is_cuda and c // h == 32 and (self.attn_drop.p == 0.0 or not self.training) and (mask is None or region is not None)
-                and not _GENERIC_ATTENTION):
+        if fused:
             nw = region.shape[0] if region is not None else 1
             out = window_attention(qkv.view(bw, n, 3, h, c // h), bias, region, self.scale, nw, self.__dict__.pop("_bias_t", None))      # csrc/win_attn.hip
             return self.proj_drop(self.proj(out))
