@@ -316,8 +316,9 @@ int ocpg_conv3x3_mfma_wgrad(const void* gz, const void* x, int N, int H, int W, 
  * points); any other value returns -1010 before anything is launched.  Arguments, geometry limits and return codes are those of the
  * un-suffixed twin, every tensor (x, w, y, cols / dy, mask_y, dx / gz, part) in that one type; scale / bias stay fp32 and the accumulation
  * fp32.  With dtype 1 they launch the very kernels the un-suffixed symbols launch (which forward here); with dtype 2 the fp16 instantiations
- * (MFMA 32x32x16 f16).  ocpg_conv3x3_mfma_wgrad_splits serves both.  The split-K forms, ocpg_conv3x3_mfma_dgrad(_masked) and the halo
- * variant have no fp16 form. */
+ * (MFMA 32x32x16 f16).  ocpg_conv3x3_mfma_wgrad_splits serves both.  The neck's split-K forward has its fp16 form below
+ * (ocpg_conv3x3_mfma_fwd_splitk_h16); the body split-K pair (ocpg_conv3x3_mfma_fwd_bn_splitk, ocpg_conv3x3_mfma_dgrad_w_splitk),
+ * ocpg_conv3x3_mfma_dgrad(_masked) and the halo variant have no fp16 form. */
 int ocpg_conv3x3_mfma_fwd_cols_h16(const void* x, const void* w, const float* scale, const float* bias, int relu, int N, int H, int W, int Cin,
                                    int Cout, int stride, void* y, void* cols, int dtype, void* stream);
 int ocpg_conv3x3_mfma_dgrad_w_h16(const void* dy, const void* w, const void* mask_y, const float* scale, int N, int H, int W, int Cin, int Cout,
@@ -331,10 +332,17 @@ int ocpg_conv3x3_mfma_wgrad_h16(const void* gz, const void* x, int N, int H, int
  * sums part[splits][N*Ho*Wo][Cout] (caller-provided scratch, fully written) and a second kernel adds them and the bias into
  * y [N,Ho,Wo,Cout] (out_dt 0 fp32 / 1 bf16).  ocpg_conv3x3_mfma_splits: the number of ranges to use for a shape (1 = the plain kernel
  * fills the chip: call ocpg_conv3x3_mfma_fwd).  cols (may be NULL): the patch matrix, as ocpg_conv3x3_mfma_fwd_cols writes it.  The input
- * gradient is ocpg_conv3x3_mfma_dgrad (its GEMM has N*H*W rows: no split needed). */
+ * gradient is ocpg_conv3x3_mfma_dgrad (its GEMM has N*H*W rows: no split needed).
+ * _h16: the same with the 16-bit storage type of x / w / cols as an argument, by the convention of the _h16 symbols above: dtype 1 =
+ * bfloat16 (the very launches of the un-suffixed symbol, which forwards here), 2 = float16 (the fp16 instantiation of the kernel); any
+ * other value returns -1010 before any other check.  out_dt is 0 (fp32) or equal to dtype; anything else returns -2000.  Every other check,
+ * limit and return code is the un-suffixed symbol's.  In fp16 the input gradient is ocpg_conv3x3_mfma_dgrad_w_h16 on the convolution's
+ * own weight with a NULL mask and a NULL scale (ocpg_conv3x3_mfma_dgrad is bf16-only). */
 int ocpg_conv3x3_mfma_splits(int N, int H, int W, int Cin, int Cout, int stride);
 int ocpg_conv3x3_mfma_fwd_splitk(const void* x, const void* w, const float* bias, int N, int H, int W, int Cin, int Cout, int stride,
                                  int splits, float* part, void* y, int out_dt, void* cols, void* stream);
+int ocpg_conv3x3_mfma_fwd_splitk_h16(const void* x, const void* w, const float* bias, int N, int H, int W, int Cin, int Cout, int stride,
+                                     int splits, float* part, void* y, int out_dt, void* cols, int dtype, void* stream);
 
 /* Dense GEMM with a per-shape plan cache over hipBLASLt -- replaces the at::mm / at::addmm / at::bmm calls behind
  * nn.Linear and the 1x1 nn.Conv2d layers on the path (models/deformable_transformer.py:236-257,313-327 FFNs,
@@ -584,10 +592,19 @@ int ocpg_bilinear_nhwc_bwd(const float* gout, int NB, int H, int W, int C, int H
  *        act = ReLU when relu != 0 (the MLPs' `F.relu(layer(x))`, models/ocpg.py:53-58)
  *   bwd: gx [R, Cin] in x's dtype (NULL: not needed), gw [Cout, Cin] bf16, gb [Cout] bf16 (NULL: no bias) from gy [R, Cout];
  *        y_relu = the forward's output when it applied the ReLU (gy is masked where y <= 0), else NULL
- * Cin must be a multiple of 64 and R <= 4096; otherwise -2000 (the caller keeps its GEMM path). */
+ * Cin must be a multiple of 64 and R <= 4096; otherwise -2000 (the caller keeps its GEMM path).
+ * _h16: the same with the 16-bit storage type as an argument (the convention of the conv _h16 symbols): dtype 1 = bfloat16 (the very
+ * launch of the un-suffixed symbol, which forwards here), 2 = float16 (the reference's --amp mode: w / b / y / gw / gb / y_relu and a
+ * non-fp32 x / gy are fp16, MFMA 32x32x16 f16, fp32 accumulation); any other value returns -1010 before any other check and before
+ * anything is launched.  An fp32 x / gy is rounded to nearest-even while it is staged; in fp16 a value past 65504 becomes inf, as ATen's
+ * cast makes it (no clamping, no saturation).  Every other check, limit and return code is the un-suffixed symbol's. */
 int ocpg_small_linear_fwd(const void* x, int x_f32, const void* w, const void* b, int R, int Cin, int Cout, int relu, void* y, void* stream);
 int ocpg_small_linear_bwd(const void* gy, int gy_f32, const void* x, int x_f32, const void* w, const void* y_relu, int R, int Cin, int Cout,
                           void* gx, void* gw, void* gb, void* stream);
+int ocpg_small_linear_fwd_h16(const void* x, int x_f32, const void* w, const void* b, int R, int Cin, int Cout, int relu, void* y, int dtype,
+                              void* stream);
+int ocpg_small_linear_bwd_h16(const void* gy, int gy_f32, const void* x, int x_f32, const void* w, const void* y_relu, int R, int Cin, int Cout,
+                              void* gx, void* gw, void* gb, int dtype, void* stream);
 /* The same for the fp32 islands (MSDeformAttn's projections over the decoder's few query rows run with autocast disabled, reference
  * models/deformable_transformer.py:329-332): x / w / b / y and every gradient fp32, exact fp32 products on the matrix cores
  * (csrc/small_linear_f32.hip).  gx NULL: not needed; gb NULL: no bias.  Cin % 64 != 0 or R > 4096: -2000. */

@@ -55,6 +55,7 @@ SIGNATURES = {
     "ocpg_conv3x3_mfma_dgrad_w_h16": [_vp, _vp, _vp, _vp] + [_int] * 6 + [_vp, _int, _vp],
     "ocpg_conv3x3_mfma_wgrad_h16": [_vp, _vp] + [_int] * 6 + [_vp, _int, _vp],
     "ocpg_conv3x3_mfma_fwd_splitk": [_vp, _vp, _vp] + [_int] * 7 + [_vp, _vp, _int, _vp, _vp],
+    "ocpg_conv3x3_mfma_fwd_splitk_h16": [_vp, _vp, _vp] + [_int] * 7 + [_vp, _vp, _int, _vp, _int, _vp],
     "ocpg_gemm": [_vp, _vp, _vp, _vp] + [_int] * 4 + [ctypes.c_longlong] * 10 + [ctypes.c_float, ctypes.c_float, _vp],
     "ocpg_gemm_plans": [],
     "ocpg_gemm_tuned": [_vp],
@@ -74,6 +75,8 @@ SIGNATURES = {
     "ocpg_bilinear_nhwc_bwd": [_vp] + [_int] * 6 + [_vp, _vp],
     "ocpg_small_linear_fwd": [_vp, _int, _vp, _vp, _int, _int, _int, _int, _vp, _vp],
     "ocpg_small_linear_bwd": [_vp, _int, _vp, _int, _vp, _vp, _int, _int, _int, _vp, _vp, _vp, _vp],
+    "ocpg_small_linear_fwd_h16": [_vp, _int, _vp, _vp, _int, _int, _int, _int, _vp, _int, _vp],
+    "ocpg_small_linear_bwd_h16": [_vp, _int, _vp, _int, _vp, _vp, _int, _int, _int, _vp, _vp, _vp, _int, _vp],
     "ocpg_small_linear_f32_fwd": [_vp, _vp, _vp, _int, _int, _int, _vp, _vp],
     "ocpg_small_linear_f32_bwd": [_vp, _vp, _vp, _int, _int, _int, _vp, _vp, _vp, _vp],
     "ocpg_layernorm_blocks": [ctypes.c_longlong],

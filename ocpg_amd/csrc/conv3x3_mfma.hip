@@ -76,7 +76,8 @@ __device__ __forceinline__ bool tap_source(const ConvGeom& g, int y, int x, int 
 #include "conv3x3_mfma_kernel.h"
 #undef CONV3X3_KERNEL
 #undef CONV3X3_ELEM
-// fp16 storage (the reference's --amp mode); instantiated for the forward and the own-weight input gradient of the shipped step
+// fp16 storage (the reference's --amp mode); instantiated for the forward, the own-weight input gradient of the shipped step and the
+// neck's split-K forward
 #define CONV3X3_KERNEL conv3x3_mfma_f16
 #define CONV3X3_ELEM Fp16
 #include "conv3x3_mfma_kernel.h"
@@ -230,7 +231,7 @@ extern "C" int ocpg_conv3x3_mfma_dgrad_w(const void* dy, const void* w, const vo
 
 namespace {
 
-// out[m][c] = act((sum_z part[z][m][c]) * scale[c] + bias[c]), zeroed where mask[m][c] <= 0  (out_dt 0 fp32 / 1 bf16; scale / bias / mask may
+// out[m][c] = act((sum_z part[z][m][c]) * scale[c] + bias[c]), zeroed where mask[m][c] <= 0  (out_dt 0 fp32 / 1 bf16 / 2 fp16; scale / bias / mask may
 // be NULL; act = ReLU when relu != 0): the epilogues of the un-split kernel (conv bias; frozen-BN affine + ReLU; the layer in front's
 // BN + ReLU backward) applied by the summing pass
 __global__ __launch_bounds__(256) void k_splitk_reduce(const float* __restrict__ part, const float* __restrict__ bias, int splits, long long MC, int Cout,
@@ -262,6 +263,10 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(const float* __restrict__
   }
   if (out_dt == 0) {
     *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + i) = a;
+  } else if (out_dt == 2) {
+    ushort4 o;
+    o.x = ocpg_h16::Fp16::bits(a.x); o.y = ocpg_h16::Fp16::bits(a.y); o.z = ocpg_h16::Fp16::bits(a.z); o.w = ocpg_h16::Fp16::bits(a.w);
+    *reinterpret_cast<ushort4*>(reinterpret_cast<unsigned short*>(out) + i) = o;
   } else {
     ushort4 o;
     o.x = __bfloat16_as_ushort(__float2bfloat16(a.x)); o.y = __bfloat16_as_ushort(__float2bfloat16(a.y));
@@ -284,12 +289,14 @@ extern "C" int ocpg_conv3x3_mfma_splits(int N, int H, int W, int Cin, int Cout, 
   return tiles < 256 ? best : 1;
 }
 
-// part [splits][N*Ho*Wo][Cout] fp32 (scratch, fully written), y [N,Ho,Wo,Cout] = conv(x, w) + bias in out_dt (0 fp32 / 1 bf16);
+// part [splits][N*Ho*Wo][Cout] fp32 (scratch, fully written), y [N,Ho,Wo,Cout] = conv(x, w) + bias in out_dt (0 fp32 / dtype);
 // cols as in ocpg_conv3x3_mfma_fwd_cols (may be NULL).  splits must be ocpg_conv3x3_mfma_splits(...) (> 1).
-extern "C" int ocpg_conv3x3_mfma_fwd_splitk(const void* x, const void* w, const float* bias, int N, int H, int W, int Cin, int Cout, int stride,
-                                            int splits, float* part, void* y, int out_dt, void* cols, void* stream) {
+// dtype: 1 = bf16 (the very launches of ocpg_conv3x3_mfma_fwd_splitk), 2 = fp16; anything else: -1010 before any launch
+extern "C" int ocpg_conv3x3_mfma_fwd_splitk_h16(const void* x, const void* w, const float* bias, int N, int H, int W, int Cin, int Cout, int stride,
+                                                int splits, float* part, void* y, int out_dt, void* cols, int dtype, void* stream) {
+  if (dtype != 1 && dtype != 2) return -1010;
   if (N < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return -1006;
-  if ((stride != 1 && stride != 2) || Cin % BK != 0 || Cout % 4 != 0 || splits < 1 || (Cin / BK) % splits != 0 || (out_dt != 0 && out_dt != 1)) return -2000;
+  if ((stride != 1 && stride != 2) || Cin % BK != 0 || Cout % 4 != 0 || splits < 1 || (Cin / BK) % splits != 0 || (out_dt != 0 && out_dt != dtype)) return -2000;
   if (N == 0) return 0;
   if (!x) return -1001;
   if (!w) return -1002;
@@ -299,12 +306,22 @@ extern "C" int ocpg_conv3x3_mfma_fwd_splitk(const void* x, const void* w, const 
   g.N = N; g.H = (H - 1) / stride + 1; g.W = (W - 1) / stride + 1; g.C = Cin; g.Hs = H; g.Ws = W; g.Cout = Cout; g.stride = stride;
   g.M = (long long)N * g.H * g.W;
   const unsigned mt = (unsigned)((g.M + BM - 1) / BM);
-  conv3x3_mfma<false, 64, true><<<dim3(mt, (unsigned)((Cout + 63) / 64), (unsigned)splits), NT, 0, (hipStream_t)stream>>>(
-      (const __hip_bfloat16*)x, (const __hip_bfloat16*)w, nullptr, nullptr, 0, g, reinterpret_cast<__hip_bfloat16*>(part), (__hip_bfloat16*)cols);
+  const dim3 grid(mt, (unsigned)((Cout + 63) / 64), (unsigned)splits);
+  if (dtype == 2)
+    conv3x3_mfma_f16<false, 64, true><<<grid, NT, 0, (hipStream_t)stream>>>((const __half*)x, (const __half*)w, nullptr, nullptr, 0, g,
+                                                                          reinterpret_cast<__half*>(part), (__half*)cols);
+  else
+    conv3x3_mfma<false, 64, true><<<grid, NT, 0, (hipStream_t)stream>>>(
+        (const __hip_bfloat16*)x, (const __hip_bfloat16*)w, nullptr, nullptr, 0, g, reinterpret_cast<__hip_bfloat16*>(part), (__hip_bfloat16*)cols);
   const long long MC = g.M * Cout;
   k_splitk_reduce<<<(unsigned)((MC / 4 + 255) / 256), 256, 0, (hipStream_t)stream>>>(part, bias, splits, MC, Cout, y, out_dt);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : -(int)e;
+}
+
+extern "C" int ocpg_conv3x3_mfma_fwd_splitk(const void* x, const void* w, const float* bias, int N, int H, int W, int Cin, int Cout, int stride,
+                                            int splits, float* part, void* y, int out_dt, void* cols, void* stream) {
+  return ocpg_conv3x3_mfma_fwd_splitk_h16(x, w, bias, N, H, W, Cin, Cout, stride, splits, part, y, out_dt, cols, 1, stream);
 }
 
 // ---- split K for the ResNet body (round 4): at 2 (1) clips per step a layer3 / layer4 convolution is 300-600 (150-300) workgroups each

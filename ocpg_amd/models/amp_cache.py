@@ -26,6 +26,7 @@ ENABLED = True      # A/B switch (tests compare against autocast's own per-op ca
 GEMM_1X1 = os.environ.get("OCPG_GEMM_1X1", "1") != "0"     # A/B switch: 1x1 convs of channels-last maps as hipBLASLt GEMMs instead of MIOpen convolutions
 GEMM_3X3 = os.environ.get("OCPG_GEMM_3X3", "0") != "0"     # A/B switch: 3x3 convs of channels-last maps as HIP im2col + one hipBLASLt GEMM
 SPLITK_3X3 = os.environ.get("OCPG_SPLITK_3X3", "1") != "0"     # A/B switch: 3x3 convs with few output pixels and a long reduction through the split-K MFMA kernel (0 = MIOpen)
+SPLITK_3X3_FP16 = os.environ.get("OCPG_SPLITK_3X3_FP16", "1") != "0"     # A/B switch: the same under fp16 autocast through the kernel's fp16 instantiation (0 = MIOpen in fp16; bf16 unchanged)
 SPLIT_K = os.environ.get("OCPG_SPLIT_K", "1") != "0"      # A/B switch: weight gradients over many rows as row-split batched GEMMs
 
 
@@ -434,11 +435,14 @@ class TokenLinearFunction(torch.autograd.Function):
 TOKEN_LINEAR_MIN_ROWS = int(os.environ.get("OCPG_TOKEN_LINEAR_MIN_ROWS", "8192"))     # rows from which a Linear goes through TokenLinearFunction (plan-cache GEMMs, row-split weight gradient)
 SMALL_LINEAR_F32 = os.environ.get("OCPG_SMALL_LINEAR_F32", "1") != "0"     # A/B switch: the fp32 islands' few-row Linears too (csrc/small_linear_f32.hip)
 SMALL_LINEAR = os.environ.get("OCPG_SMALL_LINEAR", "1") != "0"     # A/B switch: few-row Linears as one launch each way (csrc/small_linear.hip)
+SMALL_LINEAR_FP16 = os.environ.get("OCPG_SMALL_LINEAR_FP16", "1") != "0"     # A/B switch: the same under fp16 autocast (sl_fwd_f16 / sl_bwd_f16; 0 = cast + addmm, mm + mm + sum + cast in fp16; bf16 unchanged)
 
 
 class SmallLinearFunction(torch.autograd.Function):
-    """y = x W^T + b for FEW rows under bf16 autocast: one launch forward (input cast, GEMM, bias), ONE launch backward (input
-    gradient in x's dtype, weight gradient, bias gradient) instead of cast + addmm and mm + mm + sum + cast."""
+    """y = x W^T + b for FEW rows under bf16 / fp16 autocast: one launch forward (input cast, GEMM, bias), ONE launch backward (input
+    gradient in x's dtype, weight gradient, bias gradient) instead of cast + addmm and mm + mm + sum + cast.  The 16-bit storage type is
+    w's dtype: bf16 through the un-suffixed symbols (the kernels and the call census they always had), fp16 through the _h16 symbols
+    with dtype 2."""
 
     @staticmethod
     def forward(ctx, x, w, b, relu=False):
@@ -447,10 +451,18 @@ class SmallLinearFunction(torch.autograd.Function):
         x2 = x.reshape(-1, k)
         if not x2.is_contiguous():
             x2 = x2.contiguous()
-        y = torch.empty((*x.shape[:-1], co), dtype=torch.bfloat16, device=x.device)    # not a view: an in-place ReLU may follow
-        check(lib().ocpg_small_linear_fwd(x2.data_ptr(), int(x2.dtype == torch.float32), w.data_ptr(), None if b is None else b.data_ptr(),
-                                          x2.shape[0], k, co, int(relu), y.data_ptr(), torch.cuda.current_stream().cuda_stream),
-              "ocpg_small_linear_fwd")
+        if w.dtype not in (torch.bfloat16, torch.float16) or x2.dtype not in (torch.float32, w.dtype) or (b is not None and b.dtype != w.dtype):
+            raise RuntimeError(f"SmallLinearFunction: w / b must share one 16-bit dtype and x be fp32 or that dtype, got x {x2.dtype}, w {w.dtype}, "
+                               f"b {None if b is None else b.dtype}")
+        y = torch.empty((*x.shape[:-1], co), dtype=w.dtype, device=x.device)    # not a view: an in-place ReLU may follow
+        if w.dtype == torch.float16:
+            check(lib().ocpg_small_linear_fwd_h16(x2.data_ptr(), int(x2.dtype == torch.float32), w.data_ptr(), None if b is None else b.data_ptr(),
+                                                  x2.shape[0], k, co, int(relu), y.data_ptr(), 2, torch.cuda.current_stream().cuda_stream),
+                  "ocpg_small_linear_fwd_h16")
+        else:
+            check(lib().ocpg_small_linear_fwd(x2.data_ptr(), int(x2.dtype == torch.float32), w.data_ptr(), None if b is None else b.data_ptr(),
+                                              x2.shape[0], k, co, int(relu), y.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                  "ocpg_small_linear_fwd")
         if relu:
             ctx.save_for_backward(x2, w, y)
         else:
@@ -465,17 +477,23 @@ class SmallLinearFunction(torch.autograd.Function):
         ymask = ctx.saved_tensors[2] if ctx.relu else None
         co, k = w.shape
         g2 = gy.reshape(-1, co)
-        if g2.dtype not in (torch.float32, torch.bfloat16):
+        if g2.dtype not in (torch.float32, w.dtype):
             g2 = g2.float()
         if not g2.is_contiguous():
             g2 = g2.contiguous()
         gx = torch.empty_like(x2) if ctx.needs_input_grad[0] else None
         gw = torch.empty_like(w)
-        gb = torch.empty(co, dtype=torch.bfloat16, device=w.device) if ctx.has_bias else None
-        check(lib().ocpg_small_linear_bwd(g2.data_ptr(), int(g2.dtype == torch.float32), x2.data_ptr(), int(x2.dtype == torch.float32), w.data_ptr(),
-                                          None if ymask is None else ymask.data_ptr(), x2.shape[0], k, co,
-                                          None if gx is None else gx.data_ptr(), gw.data_ptr(), None if gb is None else gb.data_ptr(),
-                                          torch.cuda.current_stream().cuda_stream), "ocpg_small_linear_bwd")
+        gb = torch.empty(co, dtype=w.dtype, device=w.device) if ctx.has_bias else None
+        if w.dtype == torch.float16:
+            check(lib().ocpg_small_linear_bwd_h16(g2.data_ptr(), int(g2.dtype == torch.float32), x2.data_ptr(), int(x2.dtype == torch.float32),
+                                                  w.data_ptr(), None if ymask is None else ymask.data_ptr(), x2.shape[0], k, co,
+                                                  None if gx is None else gx.data_ptr(), gw.data_ptr(), None if gb is None else gb.data_ptr(),
+                                                  2, torch.cuda.current_stream().cuda_stream), "ocpg_small_linear_bwd_h16")
+        else:
+            check(lib().ocpg_small_linear_bwd(g2.data_ptr(), int(g2.dtype == torch.float32), x2.data_ptr(), int(x2.dtype == torch.float32), w.data_ptr(),
+                                              None if ymask is None else ymask.data_ptr(), x2.shape[0], k, co,
+                                              None if gx is None else gx.data_ptr(), gw.data_ptr(), None if gb is None else gb.data_ptr(),
+                                              torch.cuda.current_stream().cuda_stream), "ocpg_small_linear_bwd")
         return (None if gx is None else gx.view(ctx.x_shape)), gw, gb, None
 
 
@@ -524,15 +542,19 @@ def _small_linear_f32_ok(x, w, b):
 
 
 def _small_linear_ok(x, w, b):
+    """w, b and (unless fp32) x in the autocast dtype -- bf16, or fp16 (OCPG_SMALL_LINEAR_FP16); mixed 16-bit operands are never launched."""
     k = x.shape[-1]
-    return (SMALL_LINEAR and x.is_cuda and torch.is_grad_enabled() and torch.is_autocast_enabled("cuda")
-            and torch.get_autocast_dtype("cuda") == torch.bfloat16 and w.dim() == 2 and k % 64 == 0 and k <= int(os.environ.get("OCPG_SMALL_LINEAR_MAXK", "512"))
-            and x.numel() <= 1024 * k and x.dtype in (torch.float32, torch.bfloat16) and w.dtype == torch.bfloat16 and w.is_contiguous()
-            and (b is None or (b.dtype == torch.bfloat16 and b.is_contiguous())))
+    if not (SMALL_LINEAR and x.is_cuda and torch.is_grad_enabled() and torch.is_autocast_enabled("cuda")):
+        return False
+    dt = torch.get_autocast_dtype("cuda")
+    return ((dt == torch.bfloat16 or (dt == torch.float16 and SMALL_LINEAR_FP16))
+            and w.dim() == 2 and k % 64 == 0 and k <= int(os.environ.get("OCPG_SMALL_LINEAR_MAXK", "512"))
+            and x.numel() <= 1024 * k and x.dtype in (torch.float32, dt) and w.dtype == dt and w.is_contiguous()
+            and (b is None or (b.dtype == dt and b.is_contiguous())))
 
 
 def linear_relu(x, w, b):
-    """relu(linear(x, w, b)); few rows under bf16 autocast: ONE launch (the ReLU rides in the GEMM epilogue, its mask in the backward's loads)."""
+    """relu(linear(x, w, b)); few rows under bf16 / fp16 autocast: ONE launch (the ReLU rides in the GEMM epilogue, its mask in the backward's loads)."""
     if _small_linear_ok(x, w, b):
         return SmallLinearFunction.apply(x, w, b, True)
     return F.relu(linear(x, w, b))
@@ -540,7 +562,7 @@ def linear_relu(x, w, b):
 
 def linear(x, w, b):
     """F.linear; on the GPU, with >= 8192 rows and a weight that needs a gradient, through TokenLinearFunction; with few rows under
-    bf16 autocast through SmallLinearFunction."""
+    bf16 / fp16 autocast through SmallLinearFunction."""
     k = x.shape[-1]
     if _small_linear_ok(x, w, b):
         return SmallLinearFunction.apply(x, w, b)
@@ -562,6 +584,11 @@ class TokenLinear(nn.Linear):
         return linear(x, self.weight, self.bias)
 
 
+def _splitk_dtype_ok(dt):
+    """autocast dtypes whose maps the split-K 3x3 kernel serves: bf16, and fp16 unless OCPG_SPLITK_3X3_FP16=0"""
+    return dt == torch.bfloat16 or (dt == torch.float16 and SPLITK_3X3_FP16)
+
+
 class Conv2d(nn.Conv2d):
     def _is_pointwise(self):
         r = self.__dict__.get("_pointwise")
@@ -579,7 +606,7 @@ class Conv2d(nn.Conv2d):
             if x.dtype == w.dtype:
                 return Conv1x1AsGemm.apply(x, w, b)
         elif SPLITK_3X3 and x.is_cuda and x.dim() == 4 and self.kernel_size == (3, 3) and torch.is_autocast_enabled("cuda") \
-                and torch.get_autocast_dtype("cuda") == torch.bfloat16 and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16:
+                and _splitk_dtype_ok(torch.get_autocast_dtype("cuda")) and x.dtype == w.dtype == torch.get_autocast_dtype("cuda"):
             from .ops.functions import conv_bn_func
             if conv_bn_func.eligible3x3_splitk(x, self):       # few output pixels, long reduction: the neck's stride-2 level (csrc/conv3x3_mfma.hip, split-K)
                 return conv_bn_func.conv3x3_splitk(x, w, b, self.stride[0])

@@ -519,10 +519,10 @@ def conv3x3_mfma_bn_act(x, w, scale, shift, relu, stride, splits):
 
 # ---- 3x3 conv (padding 1, stride 1|2) with bias, few output pixels and a long reduction: split-K on the matrix cores -------------------------
 def eligible3x3_splitk(x, conv):
-    """The neck's extra level (models/ocpg.py:119-123): bf16 channels-last map, 3x3 / padding 1 / stride 1|2, channel counts the kernel's
+    """The neck's extra level (models/ocpg.py:119-123): bf16 or fp16 channels-last map (the caller holds the weight to the same type), 3x3 / padding 1 / stride 1|2, channel counts the kernel's
     64-wide K step and output tile serve, and a GEMM so short in rows that the plain kernel would leave the chip empty
     (ocpg_conv3x3_mfma_splits > 1)."""
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16 and conv.kernel_size == (3, 3) and conv.groups == 1
+    if not (x.is_cuda and x.dim() == 4 and x.dtype in _H16 and conv.kernel_size == (3, 3) and conv.groups == 1
             and conv.stride[0] == conv.stride[1] and conv.stride[0] in (1, 2) and conv.dilation == (1, 1) and conv.padding == (1, 1)
             and conv.padding_mode == "zeros" and x.is_contiguous(memory_format=_CL) and x.shape[1] % 64 == 0 and conv.out_channels % 64 == 0):
         return False
@@ -533,7 +533,10 @@ def eligible3x3_splitk(x, conv):
 class Conv3x3SplitK(Function):
     """y = conv3x3(x, w) + b with K split over the grid (csrc/conv3x3_mfma.hip, SPLITK) + a summing pass.  The forward keeps the patch
     matrix it gathered (the weight gradient's operand: gy^T cols, one hipBLASLt GEMM over the few rows); the input gradient is the MFMA
-    kernel on the channel-swapped weight (its GEMM has N*H*W rows: no split)."""
+    kernel on the channel-swapped weight (its GEMM has N*H*W rows: no split).
+    fp16 maps (x and w both fp16): the _h16 symbols with dtype 2 -- the forward's fp16 instantiation, and the input gradient by
+    ocpg_conv3x3_mfma_dgrad_w_h16 on the convolution's OWN weight (no mask, no scale; ocpg_conv3x3_mfma_dgrad and its transposed copy are
+    bf16-only).  The bf16 path keeps the calls and symbols it had."""
 
     @staticmethod
     def forward(ctx, x, w, b, stride):
@@ -546,15 +549,22 @@ class Conv3x3SplitK(Function):
         w2 = w.permute(0, 2, 3, 1)                                   # [co,3,3,c]: a view when the weight is channels-last
         if not w2.is_contiguous():
             w2 = w2.contiguous()
+        if not _both16(x, w):
+            raise RuntimeError(f"Conv3x3SplitK: x and w must share one 16-bit dtype, got {x.dtype} and {w.dtype}")
         splits = int(L.ocpg_conv3x3_mfma_splits(n, h, wd, c, co, stride))
         part = torch.empty((splits, m, co), dtype=torch.float32, device=x.device)
         y = torch.empty((n, co, ho, wo), dtype=x.dtype, device=x.device, memory_format=_CL)
         need_w = ctx.needs_input_grad[1]
         cols = torch.empty((m, 9 * c), dtype=x.dtype, device=x.device) if need_w else None
         bf = None if b is None else b.float()
-        check(L.ocpg_conv3x3_mfma_fwd_splitk(x.data_ptr(), w2.data_ptr(), None if bf is None else bf.data_ptr(), n, h, wd, c, co, stride, splits,
-                                             part.data_ptr(), y.data_ptr(), 1, None if cols is None else cols.data_ptr(), st),
-              "ocpg_conv3x3_mfma_fwd_splitk")
+        if x.dtype == torch.float16:
+            check(L.ocpg_conv3x3_mfma_fwd_splitk_h16(x.data_ptr(), w2.data_ptr(), None if bf is None else bf.data_ptr(), n, h, wd, c, co, stride, splits,
+                                                     part.data_ptr(), y.data_ptr(), 2, None if cols is None else cols.data_ptr(), 2, st),
+                  "ocpg_conv3x3_mfma_fwd_splitk_h16")
+        else:
+            check(L.ocpg_conv3x3_mfma_fwd_splitk(x.data_ptr(), w2.data_ptr(), None if bf is None else bf.data_ptr(), n, h, wd, c, co, stride, splits,
+                                                 part.data_ptr(), y.data_ptr(), 1, None if cols is None else cols.data_ptr(), st),
+                  "ocpg_conv3x3_mfma_fwd_splitk")
         ctx.save_for_backward(w2, cols if need_w else w2)
         ctx.meta = (n, c, h, wd, ho, wo, stride, b is not None, need_w)
         return y
@@ -568,16 +578,21 @@ class Conv3x3SplitK(Function):
         m, k = n * ho * wo, 9 * c
         L = lib()
         st = torch.cuda.current_stream().cuda_stream
-        if gy.dtype != torch.bfloat16 or not gy.is_contiguous(memory_format=_CL):
-            gy = gy.to(torch.bfloat16).contiguous(memory_format=_CL)
+        dt = _DT[w2.dtype]                  # 1 bf16 / 2 fp16: the map's (= the weight's) type; gy, gx, gw, gb and the patch matrix are of it
+        if gy.dtype != w2.dtype or not gy.is_contiguous(memory_format=_CL):
+            gy = gy.to(w2.dtype).contiguous(memory_format=_CL)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            wt = w2.permute(3, 1, 2, 0).contiguous()               # [c,3,3,co]
             gx = torch.empty((n, c, h, wd), dtype=gy.dtype, device=gy.device, memory_format=_CL)
-            check(L.ocpg_conv3x3_mfma_dgrad(gy.data_ptr(), wt.data_ptr(), n, h, wd, c, co, stride, gx.data_ptr(), st), "ocpg_conv3x3_mfma_dgrad")
+            if dt == 2:     # the weight as it lies, through the own-weight kernel's fp16 instantiation (no mask, no scale)
+                check(L.ocpg_conv3x3_mfma_dgrad_w_h16(gy.data_ptr(), w2.data_ptr(), None, None, n, h, wd, c, co, stride, gx.data_ptr(), 2, st),
+                      "ocpg_conv3x3_mfma_dgrad_w_h16")
+            else:
+                wt = w2.permute(3, 1, 2, 0).contiguous()               # [c,3,3,co]
+                check(L.ocpg_conv3x3_mfma_dgrad(gy.data_ptr(), wt.data_ptr(), n, h, wd, c, co, stride, gx.data_ptr(), st), "ocpg_conv3x3_mfma_dgrad")
         if need_w and ctx.needs_input_grad[1]:
             g2 = torch.empty((co, k), dtype=gy.dtype, device=gy.device)
-            check(L.ocpg_gemm(gy.data_ptr(), cols.data_ptr(), g2.data_ptr(), None, 1, 1, 1, 0, co, k, m, co, k, k, 1, 0, 0, 0, 1.0, 0.0, st), "ocpg_gemm")
+            check(L.ocpg_gemm(gy.data_ptr(), cols.data_ptr(), g2.data_ptr(), None, dt, dt, 1, 0, co, k, m, co, k, k, 1, 0, 0, 0, 1.0, 0.0, st), "ocpg_gemm")
             gw = g2.view(co, 3, 3, c).permute(0, 3, 1, 2)          # channels-last strides of [co, c, 3, 3]
         if has_b and ctx.needs_input_grad[2]:
             gb = gy.permute(0, 2, 3, 1).reshape(m, co).float().sum(0).to(gy.dtype)
