@@ -325,6 +325,14 @@ int ocpg_conv3x3_mfma_dgrad_w_h16(const void* dy, const void* w, const void* mas
                                   int stride, void* dx, int dtype, void* stream);
 int ocpg_conv3x3_mfma_wgrad_h16(const void* gz, const void* x, int N, int H, int W, int Cin, int Cout, int stride, void* part, int dtype,
                                 void* stream);
+/* ocpg_conv3x3_mfma_dgrad_w(_h16) for stride 2 in parity-class tiles: a 64-row tile holds input pixels of one class (y & 1, x & 1) and walks
+ * only the taps that reach it (4 for odd/odd, 2 for the mixed classes, 1 for even/even: 9 taps per 4 pixels, where the nine-tap symbols
+ * walk 36 and multiply zero rows for 27 of them).  Same arguments, checks and return codes as the nine-tap twin; stride != 2 returns -2000.
+ * dx is fully written and, for finite operands, bit-identical to the nine-tap symbol's (the same non-zero products in the same order). */
+int ocpg_conv3x3_mfma_dgrad_w_s2(const void* dy, const void* w, const void* mask_y, const float* scale, int N, int H, int W, int Cin, int Cout,
+                                 int stride, void* dx, void* stream);
+int ocpg_conv3x3_mfma_dgrad_w_s2_h16(const void* dy, const void* w, const void* mask_y, const float* scale, int N, int H, int W, int Cin, int Cout,
+                                     int stride, void* dx, int dtype, void* stream);
 
 /* Split-K form of ocpg_conv3x3_mfma_fwd for convolutions with FEW output pixels and a LONG reduction (round 4): the neck's extra level
  * input_proj[3] = nn.Conv2d(2048, 256, 3, stride=2, padding=1) (models/ocpg.py:119-123; 600 output pixels at config #2, K = 18 432) --

@@ -54,6 +54,8 @@ SIGNATURES = {
     "ocpg_conv3x3_mfma_fwd_cols_h16": [_vp, _vp, _vp, _vp] + [_int] * 7 + [_vp, _vp, _int, _vp],
     "ocpg_conv3x3_mfma_dgrad_w_h16": [_vp, _vp, _vp, _vp] + [_int] * 6 + [_vp, _int, _vp],
     "ocpg_conv3x3_mfma_wgrad_h16": [_vp, _vp] + [_int] * 6 + [_vp, _int, _vp],
+    "ocpg_conv3x3_mfma_dgrad_w_s2": [_vp, _vp, _vp, _vp] + [_int] * 6 + [_vp, _vp],
+    "ocpg_conv3x3_mfma_dgrad_w_s2_h16": [_vp, _vp, _vp, _vp] + [_int] * 6 + [_vp, _int, _vp],
     "ocpg_conv3x3_mfma_fwd_splitk": [_vp, _vp, _vp] + [_int] * 7 + [_vp, _vp, _int, _vp, _vp],
     "ocpg_conv3x3_mfma_fwd_splitk_h16": [_vp, _vp, _vp] + [_int] * 7 + [_vp, _vp, _int, _vp, _int, _vp],
     "ocpg_gemm": [_vp, _vp, _vp, _vp] + [_int] * 4 + [ctypes.c_longlong] * 10 + [ctypes.c_float, ctypes.c_float, _vp],
@@ -176,6 +178,9 @@ def collect_kernel_timing(work=None):
 
 # ---- optional call census (tests: prove WHICH entry points served a module; bench.py: launches per step by symbol) ----
 CENSUS = {"on": False, "calls": {}}
+# a symbol that is another ROW ORDER of a kernel (same arguments, bit-identical result) is also counted as the symbol it stands in for:
+# the census answers "which kernel family served this module", and that answer does not change with the row order
+CENSUS_ALSO = {"ocpg_conv3x3_mfma_dgrad_w_s2": "ocpg_conv3x3_mfma_dgrad_w", "ocpg_conv3x3_mfma_dgrad_w_s2_h16": "ocpg_conv3x3_mfma_dgrad_w_h16"}
 
 
 def census(on=True):
@@ -203,7 +208,9 @@ class _Lib:
             if CENSUS["on"]:
                 rc = fn(*a)
                 if rc == 0:
-                    CENSUS["calls"][name] = CENSUS["calls"].get(name, 0) + 1
+                    for k in (name, CENSUS_ALSO.get(name)):
+                        if k is not None:
+                            CENSUS["calls"][k] = CENSUS["calls"].get(k, 0) + 1
                 return rc
             if not (timed and _TIMING["on"]):
                 return fn(*a)

@@ -35,10 +35,8 @@ typedef ocpg_h16::f32x16 f32x16;
 // The 16-bit storage type of a kernel (h16_elem.h: storage type, MFMA opcode, final narrowing -- the staging, the transposing LDS reads
 // and the "bits as a signed short > 0" ReLU-mask test are type-agnostic), so the kernel has ONE body (conv3x3_mfma_kernel.h), included
 // once per element type.  The bf16 kernel keeps the name and signature it had.
-// STATIC_TAIL: the ragged-column tail of the 64-column epilogue indexes o[] / keep[] by a run-time j: 32 bytes of scratch per lane in
-// the bf16 kernels as they were measured, and they stay as they are; the new fp16 kernels unroll that tail (static indices, no scratch)
-struct Bf16 : ocpg_h16::Bf16 { static constexpr bool STATIC_TAIL = false; };
-struct Fp16 : ocpg_h16::Fp16 { static constexpr bool STATIC_TAIL = true; };
+using ocpg_h16::Bf16;
+using ocpg_h16::Fp16;
 
 constexpr int BM = 64, BK = 64, NT = 256;        // BN (64 or 128) is a template parameter: 64 doubles the workgroups of the under-filled shapes
 constexpr int LDS_ROW = BK + 8;        // bf16 elements per LDS row (144 B: 16-B aligned, rows 4 banks apart)
@@ -53,6 +51,7 @@ struct ConvGeom {
   int Cout;                // GEMM N
   int stride;
   long long M;             // N * H * W
+  int ctile[3] = {0, 0, 0};      // parity-class tiles (stride-2 own-weight input gradient): first tile of classes 1, 2, 3 (class 0 starts at 0)
 };
 
 // source pixel of GEMM row (n, y, x) for tap (ky, kx); false = zero padding
@@ -126,18 +125,19 @@ extern "C" int ocpg_conv3x3_mfma_fwd_cols_h16(const void* x, const void* w, cons
   const unsigned mt = (unsigned)((g.M + BM - 1) / BM);
   const bool narrow = narrow_tiles(mt, Cout);
   const dim3 grid(mt, (unsigned)(narrow ? (Cout + 63) / 64 : (Cout + 127) / 128));
-  if (dtype == 2) {
-    if (narrow)
-      conv3x3_mfma_f16<false, 64><<<grid, NT, 0, (hipStream_t)stream>>>((const __half*)x, (const __half*)w, scale, bias, relu, g, (__half*)y, (__half*)cols);
-    else
-      conv3x3_mfma_f16<false, 128><<<grid, NT, 0, (hipStream_t)stream>>>((const __half*)x, (const __half*)w, scale, bias, relu, g, (__half*)y, (__half*)cols);
-  } else if (narrow) {
-    conv3x3_mfma<false, 64><<<grid, NT, 0, (hipStream_t)stream>>>(
-        (const __hip_bfloat16*)x, (const __hip_bfloat16*)w, scale, bias, relu, g, (__hip_bfloat16*)y, (__hip_bfloat16*)cols);
-  } else {
-    conv3x3_mfma<false, 128><<<grid, NT, 0, (hipStream_t)stream>>>(
-        (const __hip_bfloat16*)x, (const __hip_bfloat16*)w, scale, bias, relu, g, (__hip_bfloat16*)y, (__hip_bfloat16*)cols);
-  }
+  // the patch-matrix stores are compiled in only where asked for: without them the forward fits three workgroups per CU
+  const hipStream_t s = (hipStream_t)stream;
+#define OCPG_FWD_LAUNCH(KERNEL, T, BN_, COLS_) \
+  KERNEL<false, BN_, false, false, COLS_><<<grid, NT, 0, s>>>((const T*)x, (const T*)w, scale, bias, relu, g, (T*)y, (T*)cols)
+#define OCPG_FWD_DISPATCH(KERNEL, T)                                              \
+  do {                                                                            \
+    if (narrow) { if (cols) OCPG_FWD_LAUNCH(KERNEL, T, 64, true); else OCPG_FWD_LAUNCH(KERNEL, T, 64, false); }   \
+    else { if (cols) OCPG_FWD_LAUNCH(KERNEL, T, 128, true); else OCPG_FWD_LAUNCH(KERNEL, T, 128, false); }        \
+  } while (0)
+  if (dtype == 2) OCPG_FWD_DISPATCH(conv3x3_mfma_f16, __half);
+  else OCPG_FWD_DISPATCH(conv3x3_mfma, __hip_bfloat16);
+#undef OCPG_FWD_DISPATCH
+#undef OCPG_FWD_LAUNCH
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : -(int)e;
 }
@@ -189,13 +189,14 @@ extern "C" int ocpg_conv3x3_mfma_dgrad_masked(const void* dy, const void* wT, co
   return e == hipSuccess ? 0 : -(int)e;
 }
 
-// The same from the convolution's OWN weight w [Cout, 3, 3, Cin] (no transposed copy; Cin % 8 == 0).
-// dtype: 1 = bf16 (the very launches of ocpg_conv3x3_mfma_dgrad_w), 2 = fp16; anything else: -1010 before any launch
-extern "C" int ocpg_conv3x3_mfma_dgrad_w_h16(const void* dy, const void* w, const void* mask_y, const float* scale, int N, int H, int W, int Cin,
-                                             int Cout, int stride, void* dx, int dtype, void* stream) {
+namespace {
+
+// The input gradient from the convolution's OWN weight; classes: parity-class tiles (stride 2 only)
+int dgrad_w_launch(const void* dy, const void* w, const void* mask_y, const float* scale, int N, int H, int W, int Cin, int Cout, int stride, void* dx,
+                   int dtype, bool classes, void* stream) {
   if (dtype != 1 && dtype != 2) return -1010;
   if (N < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return -1006;
-  if ((stride != 1 && stride != 2) || Cout % BK != 0 || Cin % 8 != 0) return -2000;
+  if ((stride != 1 && stride != 2) || Cout % BK != 0 || Cin % 8 != 0 || (classes && stride != 2)) return -2000;
   if (N == 0) return 0;
   if (!dy) return -1001;
   if (!w) return -1002;
@@ -203,30 +204,58 @@ extern "C" int ocpg_conv3x3_mfma_dgrad_w_h16(const void* dy, const void* w, cons
   ConvGeom g;
   g.N = N; g.H = H; g.W = W; g.C = Cout; g.Hs = (H - 1) / stride + 1; g.Ws = (W - 1) / stride + 1; g.Cout = Cin; g.stride = stride;
   g.M = (long long)N * H * W;
-  const unsigned mt = (unsigned)((g.M + BM - 1) / BM);
-  const bool narrow = narrow_tiles(mt, Cin);
-  const dim3 grid(mt, (unsigned)(narrow ? (Cin + 63) / 64 : (Cin + 127) / 128));
-  if (dtype == 2) {
-    if (narrow)
-      conv3x3_mfma_f16<true, 64, false, true><<<grid, NT, 0, (hipStream_t)stream>>>((const __half*)dy, (const __half*)w, scale, nullptr, 0, g, (__half*)dx, nullptr,
-                                                                             (const __half*)mask_y);
-    else
-      conv3x3_mfma_f16<true, 128, false, true><<<grid, NT, 0, (hipStream_t)stream>>>((const __half*)dy, (const __half*)w, scale, nullptr, 0, g, (__half*)dx, nullptr,
-                                                                              (const __half*)mask_y);
-  } else if (narrow) {
-    conv3x3_mfma<true, 64, false, true><<<grid, NT, 0, (hipStream_t)stream>>>(
-        (const __hip_bfloat16*)dy, (const __hip_bfloat16*)w, scale, nullptr, 0, g, (__hip_bfloat16*)dx, nullptr, (const __hip_bfloat16*)mask_y);
-  } else {
-    conv3x3_mfma<true, 128, false, true><<<grid, NT, 0, (hipStream_t)stream>>>(
-        (const __hip_bfloat16*)dy, (const __hip_bfloat16*)w, scale, nullptr, 0, g, (__hip_bfloat16*)dx, nullptr, (const __hip_bfloat16*)mask_y);
+  unsigned mt = (unsigned)((g.M + BM - 1) / BM);
+  const bool narrow = narrow_tiles(mt, Cin);      // (classes: the tile width the nine-tap launch of this shape has)
+  if (classes) {      // tiles of one parity class (y & 1, x & 1) each, the heavy class first: (1,1), (0,1), (1,0), (0,0); an empty class has none
+    long long t = 0;
+    for (int k = 0; k < 4; ++k) {
+      const int cpy = (k & 1) ^ 1, cpx = k < 2;
+      t += ((long long)N * ((H - cpy + 1) / 2) * ((W - cpx + 1) / 2) + BM - 1) / BM;
+      if (k < 3) g.ctile[k] = (int)t;
+    }
+    mt = (unsigned)t;
   }
+  const dim3 grid(mt, (unsigned)(narrow ? (Cin + 63) / 64 : (Cin + 127) / 128));
+  const hipStream_t s = (hipStream_t)stream;
+#define OCPG_DGRAD_LAUNCH(KERNEL, T, BN_, CLS_) \
+  KERNEL<true, BN_, false, true, false, CLS_><<<grid, NT, 0, s>>>((const T*)dy, (const T*)w, scale, nullptr, 0, g, (T*)dx, nullptr, (const T*)mask_y)
+#define OCPG_DGRAD_DISPATCH(KERNEL, T)                                            \
+  do {                                                                            \
+    if (narrow) { if (classes) OCPG_DGRAD_LAUNCH(KERNEL, T, 64, true); else OCPG_DGRAD_LAUNCH(KERNEL, T, 64, false); }   \
+    else { if (classes) OCPG_DGRAD_LAUNCH(KERNEL, T, 128, true); else OCPG_DGRAD_LAUNCH(KERNEL, T, 128, false); }        \
+  } while (0)
+  if (dtype == 2) OCPG_DGRAD_DISPATCH(conv3x3_mfma_f16, __half);
+  else OCPG_DGRAD_DISPATCH(conv3x3_mfma, __hip_bfloat16);
+#undef OCPG_DGRAD_DISPATCH
+#undef OCPG_DGRAD_LAUNCH
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : -(int)e;
+}
+
+}  // namespace
+
+// The same from the convolution's OWN weight w [Cout, 3, 3, Cin] (no transposed copy; Cin % 8 == 0).
+// dtype: 1 = bf16 (the very launches of ocpg_conv3x3_mfma_dgrad_w), 2 = fp16; anything else: -1010 before any launch
+extern "C" int ocpg_conv3x3_mfma_dgrad_w_h16(const void* dy, const void* w, const void* mask_y, const float* scale, int N, int H, int W, int Cin,
+                                             int Cout, int stride, void* dx, int dtype, void* stream) {
+  return dgrad_w_launch(dy, w, mask_y, scale, N, H, W, Cin, Cout, stride, dx, dtype, false, stream);
 }
 
 extern "C" int ocpg_conv3x3_mfma_dgrad_w(const void* dy, const void* w, const void* mask_y, const float* scale, int N, int H, int W, int Cin, int Cout,
                                          int stride, void* dx, void* stream) {
   return ocpg_conv3x3_mfma_dgrad_w_h16(dy, w, mask_y, scale, N, H, W, Cin, Cout, stride, dx, 1, stream);
+}
+
+// The same for stride 2 (any other stride: -2000) in parity-class tiles: every tile walks only the taps that reach its pixels' class
+// (9 taps per 4 pixels instead of 36); bit-identical to the nine-tap symbols for finite operands
+extern "C" int ocpg_conv3x3_mfma_dgrad_w_s2_h16(const void* dy, const void* w, const void* mask_y, const float* scale, int N, int H, int W, int Cin,
+                                                int Cout, int stride, void* dx, int dtype, void* stream) {
+  return dgrad_w_launch(dy, w, mask_y, scale, N, H, W, Cin, Cout, stride, dx, dtype, true, stream);
+}
+
+extern "C" int ocpg_conv3x3_mfma_dgrad_w_s2(const void* dy, const void* w, const void* mask_y, const float* scale, int N, int H, int W, int Cin,
+                                            int Cout, int stride, void* dx, void* stream) {
+  return ocpg_conv3x3_mfma_dgrad_w_s2_h16(dy, w, mask_y, scale, N, H, W, Cin, Cout, stride, dx, 1, stream);
 }
 
 namespace {
@@ -307,12 +336,18 @@ extern "C" int ocpg_conv3x3_mfma_fwd_splitk_h16(const void* x, const void* w, co
   g.M = (long long)N * g.H * g.W;
   const unsigned mt = (unsigned)((g.M + BM - 1) / BM);
   const dim3 grid(mt, (unsigned)((Cout + 63) / 64), (unsigned)splits);
-  if (dtype == 2)
+  if (dtype == 2 && cols)
+    conv3x3_mfma_f16<false, 64, true, false, true><<<grid, NT, 0, (hipStream_t)stream>>>((const __half*)x, (const __half*)w, nullptr, nullptr, 0, g,
+                                                                                       reinterpret_cast<__half*>(part), (__half*)cols);
+  else if (dtype == 2)
     conv3x3_mfma_f16<false, 64, true><<<grid, NT, 0, (hipStream_t)stream>>>((const __half*)x, (const __half*)w, nullptr, nullptr, 0, g,
-                                                                          reinterpret_cast<__half*>(part), (__half*)cols);
+                                                                          reinterpret_cast<__half*>(part), nullptr);
+  else if (cols)
+    conv3x3_mfma<false, 64, true, false, true><<<grid, NT, 0, (hipStream_t)stream>>>(
+        (const __hip_bfloat16*)x, (const __hip_bfloat16*)w, nullptr, nullptr, 0, g, reinterpret_cast<__hip_bfloat16*>(part), (__hip_bfloat16*)cols);
   else
     conv3x3_mfma<false, 64, true><<<grid, NT, 0, (hipStream_t)stream>>>(
-        (const __hip_bfloat16*)x, (const __hip_bfloat16*)w, nullptr, nullptr, 0, g, reinterpret_cast<__hip_bfloat16*>(part), (__hip_bfloat16*)cols);
+        (const __hip_bfloat16*)x, (const __hip_bfloat16*)w, nullptr, nullptr, 0, g, reinterpret_cast<__hip_bfloat16*>(part), nullptr);
   const long long MC = g.M * Cout;
   k_splitk_reduce<<<(unsigned)((MC / 4 + 255) / 256), 256, 0, (hipStream_t)stream>>>(part, bias, splits, MC, Cout, y, out_dt);
   const hipError_t e = hipGetLastError();

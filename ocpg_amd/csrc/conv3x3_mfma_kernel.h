@@ -12,7 +12,13 @@
 // the input channel, so a K step's B tile is 64 weight ROWS (k) x BN contiguous input channels (n): it is staged as it lies, [k][n], and
 // the MFMA fragments -- 8 consecutive k of one n -- are read TRANSPOSED with gfx950's ds_read_b64_tr_b16 (per 16-lane group a 4-row x
 // 16-column block, delivered column-major: lane 4q + p supplies row q, columns 4p..4p+3, lane i receives column i of the 4 rows).
-template <bool DGRAD, int BN, bool SPLITK = false, bool BTR = false>
+// COLS (forward only): the launch also writes the patch matrix (cols).  A template parameter, not a run-time test of the pointer: the
+// forward without it keeps no patch-matrix column and no store address live through the K loop and fits three workgroups per CU.
+// CLS (own-weight input gradient of a stride-2 convolution): a 64-row tile holds input pixels of ONE parity class (y & 1, x & 1), and its
+// K loop walks only the taps that reach that class (4, 2, 2 or 1 of the 9; the other taps' rows are all zero padding).  blockIdx.x runs
+// over the classes' tile ranges (g.ctile), the heavy class first: (1,1), (0,1), (1,0), (0,0).  The non-zero products of an output element
+// and their order are those of the nine-tap walk, so the result is bit-identical for finite operands.
+template <bool DGRAD, int BN, bool SPLITK = false, bool BTR = false, bool COLS = false, bool CLS = false>
 __global__ __launch_bounds__(NT) void CONV3X3_KERNEL(const CONV3X3_ELEM::T* __restrict__ x, const CONV3X3_ELEM::T* __restrict__ w,
                                                      const float* __restrict__ scale, const float* __restrict__ bias, int relu, ConvGeom g,
                                                      CONV3X3_ELEM::T* __restrict__ y, CONV3X3_ELEM::T* __restrict__ cols,
@@ -23,6 +29,8 @@ __global__ __launch_bounds__(NT) void CONV3X3_KERNEL(const CONV3X3_ELEM::T* __re
   // does the frozen-BN + ReLU backward of the layer in front (gz = gx * scale[c] * [y_prev > 0], csrc/bn_act.hip's job until round 3)
   static_assert(!SPLITK || BN == 64, "the split-K epilogue is the 64-column one");
   static_assert(!BTR || DGRAD, "the untransposed weight operand is the input gradient's");
+  static_assert(!COLS || !DGRAD, "the patch matrix is the forward's");
+  static_assert(!CLS || (BTR && !SPLITK), "parity-class tiles are the own-weight input gradient's");
   constexpr int BROW = BN + 8;           // BTR: LDS row of the [k][n] B tile (bf16 elements; 16-byte aligned, rows 4 banks apart)
   constexpr int BSEG = BN / 8;           // BTR: 16-byte segments per staged k row
   static_assert(BK * BROW <= BN * LDS_ROW, "the [k][n] image fits the [n][k] one's buffer");
@@ -38,29 +46,44 @@ __global__ __launch_bounds__(NT) void CONV3X3_KERNEL(const CONV3X3_ELEM::T* __re
   short (*Bs)[BN * LDS_ROW] = reinterpret_cast<short (*)[BN * LDS_ROW]>(smem + 2 * BM * LDS_ROW);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave & 1, wn = wave >> 1;                 // wave tile: rows wm*32.., cols wn*64..
-  const long long m0 = (long long)blockIdx.x * BM;
+  // CLS: class k of this tile, its parity (cpy, cpx), extents and tap list (4 bits per tap, ascending); m0 counts pixels WITHIN the class
+  int cpy = 0, cpx = 0, ntaps = 9;
+  unsigned taplist = 0;
+  int tile = blockIdx.x;
+  if constexpr (CLS) {
+    const int k = (tile >= g.ctile[0]) + (tile >= g.ctile[1]) + (tile >= g.ctile[2]);
+    if (k > 0) tile -= g.ctile[k - 1];
+    cpy = (k & 1) ^ 1;
+    cpx = k < 2;
+    ntaps = k == 0 ? 4 : k == 3 ? 1 : 2;
+    taplist = k == 0 ? 0x8620u : k == 1 ? 0x53u : k == 2 ? 0x71u : 0x4u;      // ky = 1 - cpy (+2 when cpy), kx = 1 - cpx (+2 when cpx)
+  }
+  const int rH = CLS ? (g.H - cpy + 1) / 2 : g.H, rW = CLS ? (g.W - cpx + 1) / 2 : g.W;      // the map the tile's rows enumerate
+  const long long rM = CLS ? (long long)g.N * rH * rW : g.M;
+  const long long m0 = (long long)tile * BM;
   const int n0 = blockIdx.y * BN;
   // ---- staging identity: 16-B segment sseg of rows srow + i * ROWS_PER_PASS (A: i < A_L, B: i < B_L)
   const int srow = tid / SEGS, sseg = tid % SEGS;
   int pn[A_L], py[A_L], px[A_L];
   bool row_ok[A_L];
   {
-    const int hw = g.H * g.W;
+    const int hw = rH * rW;
 #pragma unroll
     for (int i = 0; i < A_L; ++i) {
       const long long mrow = m0 + srow + i * ROWS_PER_PASS;
-      row_ok[i] = mrow < g.M;
+      row_ok[i] = mrow < rM;
       const long long mr = row_ok[i] ? mrow : 0;
       pn[i] = (int)(mr / hw);
       const int r = (int)(mr - (long long)pn[i] * hw);
-      py[i] = r / g.W;
-      px[i] = r - py[i] * g.W;
+      py[i] = r / rW;
+      px[i] = r - py[i] * rW;
+      if constexpr (CLS) { py[i] = 2 * py[i] + cpy; px[i] = 2 * px[i] + cpx; }
     }
   }
   const int C = g.C, ksteps_per_tap = C / BK;
   const int cps = SPLITK ? ksteps_per_tap / (int)gridDim.z : ksteps_per_tap;      // 64-channel chunks of this workgroup (the host made it divide)
   const int c_lo = SPLITK ? (int)blockIdx.z * cps : 0, c_hi = c_lo + cps;
-  const int ksteps = 9 * cps;
+  const int ksteps = (CLS ? ntaps : 9) * cps;
   const long long wrow_stride = 9LL * C;                   // elements between consecutive GEMM-N rows of the weight operand
   const T* wp[B_L];                                        // rows past Cout are clamped: their columns are never stored
 #pragma unroll
@@ -77,7 +100,7 @@ __global__ __launch_bounds__(NT) void CONV3X3_KERNEL(const CONV3X3_ELEM::T* __re
   // (not a fraction of one) to come back -- at ~1 workgroup per CU (300 workgroups for ResNet-101's layer3 shape) nothing
   // else hides it.  Loads are unconditional (clamped address, zeroed at park time): a load inside a branch gets its own
   // s_waitcnt and serialises the batch.
-  struct Regs { uint4 a[A_L], b[B_L]; unsigned z; int coff; };     // z bit i: A row i of this set is zero padding; coff: its column in the patch matrix (-1: past the end)
+  struct Regs { uint4 a[A_L], b[B_L]; unsigned z; int coff; };     // z bit i: A row i of this set is zero padding; coff (COLS only): its column in the patch matrix (-1: past the end)
   Regs S0, S1;
   int f_tap = 0, f_c = c_lo;                               // K position of the NEXT fetch (fetches are issued in K order)
   // Fetches are UNCONDITIONAL, also past the last K step (clamped to the last tap: valid memory, never parked into a buffer that is
@@ -89,10 +112,10 @@ __global__ __launch_bounds__(NT) void CONV3X3_KERNEL(const CONV3X3_ELEM::T* __re
     // K order: the nine taps of one 64-channel chunk, then the next chunk -- consecutive steps then read the SAME 128-byte lines of
     // neighbouring pixels (a tap shifts the tile by one pixel or one row), which the L1 still holds; tap-major order re-read every
     // line from L2 nine times, and the launch is bound by the CU's L1-miss bandwidth (10 B/cycle with one workgroup per CU, 19 with three)
-    const int tap = f_tap, fc = min(f_c, c_hi - 1);
+    const int tap = CLS ? (int)((taplist >> (4 * f_tap)) & 15u) : f_tap, fc = min(f_c, c_hi - 1);      // f_tap < ntaps also past the end
     const int ky = (tap * 11) >> 5, kx = tap - ky * 3;      // tap / 3 for tap < 9
     const int c0 = fc * BK + sseg * 8;
-    R.coff = f_c < c_hi ? tap * C + c0 : -1;
+    if constexpr (COLS) R.coff = f_c < c_hi ? tap * C + c0 : -1;
     z = 0;
 #pragma unroll
     for (int i = 0; i < A_L; ++i) {
@@ -104,7 +127,7 @@ __global__ __launch_bounds__(NT) void CONV3X3_KERNEL(const CONV3X3_ELEM::T* __re
     const long long woff = BTR ? (long long)fc * BK * (9LL * g.Cout) + (long long)tap * g.Cout : (long long)tap * C + fc * BK;
 #pragma unroll
     for (int i = 0; i < B_L; ++i) bq[i] = *reinterpret_cast<const uint4*>(wp[i] + woff);
-    if (++f_tap == 9) { f_tap = 0; ++f_c; }
+    if (++f_tap == (CLS ? ntaps : 9)) { f_tap = 0; ++f_c; }
   };
   auto park = [&](int buf, const Regs& R) {
     const uint4 (&a)[A_L] = R.a; const uint4 (&bq)[B_L] = R.b; const unsigned z = R.z;
@@ -120,10 +143,10 @@ __global__ __launch_bounds__(NT) void CONV3X3_KERNEL(const CONV3X3_ELEM::T* __re
         *reinterpret_cast<uint4*>(&Bs[buf][(srow + i * ROWS_PER_PASS) * LDS_ROW + sseg * 8]) = bq[i];
       }
     }
-    if constexpr (!DGRAD) {
+    if constexpr (COLS) {
       // the gathered A tiles ARE the rows of the patch (im2col) matrix the weight gradient contracts with: the column-0 workgroups
       // write them out on the way (16 bytes per thread and row) and the backward needs no im2col pass
-      if (cols && blockIdx.y == 0 && R.coff >= 0) {
+      if (blockIdx.y == 0 && R.coff >= 0) {
 #pragma unroll
         for (int i = 0; i < A_L; ++i)
           if (row_ok[i])
@@ -183,7 +206,8 @@ __global__ __launch_bounds__(NT) void CONV3X3_KERNEL(const CONV3X3_ELEM::T* __re
     }
   };
   // Three register sets rotate (step s waits in set s % 3), two LDS buffers alternate (step s is parked into buffer s % 2);
-  // ksteps = 9 * C / BK is a multiple of 3.  A load has three compute phases to come back: one workgroup alone on a CU measured
+  // ksteps = 9 * C / BK is a multiple of 3 (CLS: ntaps * C / BK need not be: a step past ksteps parks a clamped fetch into a buffer
+  // nothing reads and skips its compute).  A load has three compute phases to come back: one workgroup alone on a CU measured
   // 0.65 us per K step with two sets (= half a load's round trip under load), and the layer3 launch has only 2.3 workgroups per CU.
   static_assert(NSETS == 3, "the k loop below is written for three register sets");
   Regs S2;
@@ -203,6 +227,17 @@ __global__ __launch_bounds__(NT) void CONV3X3_KERNEL(const CONV3X3_ELEM::T* __re
     step(ks, S1);
     step(ks + 1, S2);
     step(ks + 2, S0);
+  }
+  // CLS: tile row -> row of dx / mask (-1: past the class's last pixel), through LDS behind the two tile images of the reduction below
+  long long* rowmap = reinterpret_cast<long long*>(smem + 4 * 4096);
+  static_assert(!CLS || sizeof(smem) >= 2 * 4096 * sizeof(float) + BM * sizeof(long long), "the row map lies behind the tile images");
+  if constexpr (CLS) {
+    if (tid < BM) {
+      const long long q = m0 + tid;
+      const int hw = rH * rW, qn = (int)(q / hw), r = (int)(q - (long long)qn * hw), qy = r / rW, qx = r - qy * rW;
+      rowmap[tid] = q < rM ? ((long long)qn * g.H + 2 * qy + cpy) * g.W + 2 * qx + cpx : -1;
+    }
+    if constexpr (!KSPLIT) __syncthreads();      // (the 64-column form has its reduction's barriers in between)
   }
   if constexpr (KSPLIT) {
     // ---- sum the four waves' partial 64 x 64 tiles through LDS (the K loop ended with a barrier: the staging buffers are free).
@@ -231,8 +266,8 @@ __global__ __launch_bounds__(NT) void CONV3X3_KERNEL(const CONV3X3_ELEM::T* __re
     __syncthreads();
     // ---- epilogue by all 256 threads: thread = (tile row m, 16 consecutive columns) -> one 32-byte store
     const int m = tid >> 2, nq = (tid & 3) * 16;
-    const long long row = m0 + m;
-    if (row < g.M) {
+    const long long row = CLS ? rowmap[m] : m0 + m;
+    if (CLS ? row >= 0 : row < g.M) {
       const int r = (m & 3) + 4 * ((m & 31) >> 3), h = ((m & 31) >> 2) & 1, t0 = (m >> 5) * 2 + (nq >> 5);
       const float* src = red + (t0 * 16 + r) * 64 + (nq & 31) + 32 * h;
       const int col0 = n0 + nq;
@@ -274,12 +309,10 @@ __global__ __launch_bounds__(NT) void CONV3X3_KERNEL(const CONV3X3_ELEM::T* __re
           const bf16x8 lo = *reinterpret_cast<const bf16x8*>(mk), hi = *reinterpret_cast<const bf16x8*>(mk + 8);
 #pragma unroll
           for (int j = 0; j < 8; ++j) { keep[j] = lo[j] > 0; keep[8 + j] = hi[j] > 0; }      // bf16 / fp16 > 0 <=> its bits as a signed short > 0
-        } else if constexpr (E::STATIC_TAIL) {
+        } else {      // static indices into keep[] / o[]: a run-time j put o[] into scratch
 #pragma unroll
           for (int j = 0; j < 16; ++j)
             if (col0 + j < g.Cout) keep[j] = reinterpret_cast<const short*>(mk)[j] > 0;
-        } else {
-          for (int j = 0; j < 16 && col0 + j < g.Cout; ++j) keep[j] = reinterpret_cast<const short*>(mk)[j] > 0;
         }
       }
 #pragma unroll
@@ -296,12 +329,10 @@ __global__ __launch_bounds__(NT) void CONV3X3_KERNEL(const CONV3X3_ELEM::T* __re
         for (int j = 0; j < 8; ++j) { lo[j] = o[j]; hi[j] = o[8 + j]; }
         *reinterpret_cast<bf16x8*>(dst) = lo;
         *reinterpret_cast<bf16x8*>(dst + 8) = hi;
-      } else if constexpr (E::STATIC_TAIL) {
+      } else {
 #pragma unroll
         for (int j = 0; j < 16; ++j)
           if (col0 + j < g.Cout) reinterpret_cast<short*>(dst)[j] = o[j];
-      } else {
-        for (int j = 0; j < 16 && col0 + j < g.Cout; ++j) reinterpret_cast<short*>(dst)[j] = o[j];
       }
     }
     return;
@@ -314,10 +345,11 @@ __global__ __launch_bounds__(NT) void CONV3X3_KERNEL(const CONV3X3_ELEM::T* __re
     const float sv = scale ? scale[col] : 1.f, bv = bias ? bias[col] : 0.f;      // frozen-BN affine / conv bias in the epilogue
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const long long row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+      const int m = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+      const long long row = CLS ? rowmap[m] : m0 + m;
       float v = acc[j][r] * sv + bv;
       if (relu) v = fmaxf(v, 0.f);
-      if (row < g.M) {
+      if (CLS ? row >= 0 : row < g.M) {
         if (mask && !(reinterpret_cast<const short*>(mask)[row * g.Cout + col] > 0)) v = 0.f;
         y[row * g.Cout + col] = E::narrow(v);
       }

@@ -384,6 +384,7 @@ def eligible3x3_mfma(x, conv):
 BODY_SPLITK = os.environ.get("OCPG_CONV3X3_SPLITK", "0") != "0"     # opt-in (-1 = where the tile grid is small, n = force n): split-K forward / input gradient of the body's 3x3 convs; measured +0.45 ms per step at 2 clips, neutral at 1 (r4)
 WGRAD_OWN = os.environ.get("OCPG_WGRAD_OWN", "1") != "0"     # A/B switch: conv3x3_mfma's weight gradient by csrc/conv3x3_wgrad.hip (0 = im2col + row-split GEMM)
 DGRAD_OWN_WEIGHT = os.environ.get("OCPG_DGRAD_OWN_WEIGHT", "1") != "0"     # A/B switch: conv3x3_mfma's input gradient reads the weight untransposed
+DGRAD_S2_CLASSES = os.environ.get("OCPG_DGRAD_S2_CLASSES", "1") != "0"     # A/B switch: the stride-2 own-weight input gradient in parity-class tiles (only the taps that reach a pixel; bit-identical)
 _MFMA_MIN_C = int(os.environ.get("OCPG_MFMA_CONV3X3_MIN_C", "128"))     # 64 also serves layer1 (frozen: forward only), measured 0.08 ms/step SLOWER than MIOpen there (r4)
 
 
@@ -463,16 +464,19 @@ class Conv3x3MfmaBNAct(Function):
             tok = ctx.premask       # x IS the layer in front's bn + ReLU output: its backward rides in this kernel's epilogue
             mask_ptr, scale_ptr = (x.data_ptr(), tok["scale"].data_ptr()) if tok is not None else (None, None)
             sp = int(L.ocpg_conv3x3_mfma_body_splits(n * h * wd, c, co)) if (BODY_SPLITK and DGRAD_OWN_WEIGHT and c % 8 == 0 and not fp16) else 1
+            s2 = stride == 2 and DGRAD_S2_CLASSES       # parity-class tiles: the same result without the taps that only meet zero rows
             if fp16:        # the forward admitted fp16 only with the own-weight kernel selected; its fp16 instantiation
-                check(L.ocpg_conv3x3_mfma_dgrad_w_h16(gz.data_ptr(), w2.data_ptr(), mask_ptr, scale_ptr, n, h, wd, c, co, stride, gx.data_ptr(), 2, st),
-                      "ocpg_conv3x3_mfma_dgrad_w_h16")
+                fn = L.ocpg_conv3x3_mfma_dgrad_w_s2_h16 if s2 else L.ocpg_conv3x3_mfma_dgrad_w_h16
+                check(fn(gz.data_ptr(), w2.data_ptr(), mask_ptr, scale_ptr, n, h, wd, c, co, stride, gx.data_ptr(), 2, st),
+                      "ocpg_conv3x3_mfma_dgrad_w_s2_h16" if s2 else "ocpg_conv3x3_mfma_dgrad_w_h16")
             elif sp > 1:
                 part = torch.empty((sp, n * h * wd, c), dtype=torch.float32, device=y.device)
                 check(L.ocpg_conv3x3_mfma_dgrad_w_splitk(gz.data_ptr(), w2.data_ptr(), mask_ptr, scale_ptr, n, h, wd, c, co, stride, sp, part.data_ptr(),
                                                          gx.data_ptr(), st), "ocpg_conv3x3_mfma_dgrad_w_splitk")
             elif DGRAD_OWN_WEIGHT and c % 8 == 0:      # the weight as it lies ([co,3,3,c]): transposing LDS reads, no per-step transposed copy
-                check(L.ocpg_conv3x3_mfma_dgrad_w(gz.data_ptr(), w2.data_ptr(), mask_ptr, scale_ptr, n, h, wd, c, co, stride, gx.data_ptr(), st),
-                      "ocpg_conv3x3_mfma_dgrad_w")
+                fn = L.ocpg_conv3x3_mfma_dgrad_w_s2 if s2 else L.ocpg_conv3x3_mfma_dgrad_w
+                check(fn(gz.data_ptr(), w2.data_ptr(), mask_ptr, scale_ptr, n, h, wd, c, co, stride, gx.data_ptr(), st),
+                      "ocpg_conv3x3_mfma_dgrad_w_s2" if s2 else "ocpg_conv3x3_mfma_dgrad_w")
             else:
                 wt = w2.permute(3, 1, 2, 0).contiguous()               # [c,3,3,co]
                 check(L.ocpg_conv3x3_mfma_dgrad_masked(gz.data_ptr(), wt.data_ptr(), mask_ptr, scale_ptr, n, h, wd, c, co, stride, gx.data_ptr(), st),
@@ -585,8 +589,10 @@ class Conv3x3SplitK(Function):
         if ctx.needs_input_grad[0]:
             gx = torch.empty((n, c, h, wd), dtype=gy.dtype, device=gy.device, memory_format=_CL)
             if dt == 2:     # the weight as it lies, through the own-weight kernel's fp16 instantiation (no mask, no scale)
-                check(L.ocpg_conv3x3_mfma_dgrad_w_h16(gy.data_ptr(), w2.data_ptr(), None, None, n, h, wd, c, co, stride, gx.data_ptr(), 2, st),
-                      "ocpg_conv3x3_mfma_dgrad_w_h16")
+                s2 = stride == 2 and DGRAD_S2_CLASSES
+                fn = L.ocpg_conv3x3_mfma_dgrad_w_s2_h16 if s2 else L.ocpg_conv3x3_mfma_dgrad_w_h16
+                check(fn(gy.data_ptr(), w2.data_ptr(), None, None, n, h, wd, c, co, stride, gx.data_ptr(), 2, st),
+                      "ocpg_conv3x3_mfma_dgrad_w_s2_h16" if s2 else "ocpg_conv3x3_mfma_dgrad_w_h16")
             else:
                 wt = w2.permute(3, 1, 2, 0).contiguous()               # [c,3,3,co]
                 check(L.ocpg_conv3x3_mfma_dgrad(gy.data_ptr(), wt.data_ptr(), n, h, wd, c, co, stride, gx.data_ptr(), st), "ocpg_conv3x3_mfma_dgrad")

@@ -1,7 +1,8 @@
 """Micro-benchmark: csrc/conv3x3_mfma.hip (fwd + BN/ReLU epilogue; bwd = bn_act_bwd + MFMA dgrad + im2col/GEMM wgrad) against
 MIOpen's conv + the frozen-BN kernel, at the ResNet-101 3x3 shapes of BASELINE config #2 (10 frames, channels-last).
 --dtype bf16 (default) | fp16: the storage type of that comparison.
---kernels: instead, one JSON line per own kernel (forward, own-weight input gradient with the mask / scale epilogue, weight gradient)
+--kernels: instead, one JSON line per own kernel (forward, own-weight input gradient with the mask / scale epilogue -- at stride 2 both
+the nine-tap walk, dgrad_w, and the parity-class tiles, dgrad_w_s2 --, weight gradient)
 through the C ABI (the _h16 entry points) at every 3x3 site shape of ResNet-101 at 2 clips (20 frames), HIP events around the call, median
 of 30, warm (back to back) and cold (1 GiB written between calls), each shape as bf16, fp16, bf16 ("rep" 0 / 1): the two bf16 figures of
 one call are the run-to-run spread the fp16 figure is read against."""
@@ -62,7 +63,11 @@ def kernel_lines():
             def wgrad():
                 assert L.ocpg_conv3x3_mfma_wgrad_h16(gz.data_ptr(), x.data_ptr(), n, h, w, c, c, s, part.data_ptr(), code, st) == 0
 
-            for name, fn in (("fwd", fwd), ("dgrad_w", dgrad), ("wgrad", wgrad)):
+            def dgrad_s2():     # stride 2 only: the same input gradient in parity-class tiles (what the step runs by default)
+                assert L.ocpg_conv3x3_mfma_dgrad_w_s2_h16(gz.data_ptr(), wt.data_ptr(), x.data_ptr(), scale.data_ptr(), n, h, w, c, c, s, dx.data_ptr(),
+                                                          code, st) == 0
+
+            for name, fn in (("fwd", fwd), ("dgrad_w", dgrad)) + ((("dgrad_w_s2", dgrad_s2),) if s == 2 else ()) + (("wgrad", wgrad),):
                 for _ in range(3):
                     fn()
                 torch.cuda.synchronize()
