@@ -114,6 +114,30 @@ int ocpg_msda_bwd_f64(const double* value, const int64_t* shapes, const int64_t*
                       int N, int S, int M, int D, int L, int Lq, int P,
                       double* grad_value, double* grad_loc, double* grad_attn, void* stream);
 
+/* SAMPLE FIRST, PROJECT AFTERWARDS (csrc/msda_sample_first.hip): the module's value_proj + padding fill + op for calls with few queries
+ * (cross-attention: Lq << S), float32.  Sampling is linear in value and value_proj is the same map for every token, so
+ *   out[n, q, h*D..] = s[n, q, h, :] . Wv[h*D.., :]^T + beta[n, q, h] * bv[h*D..]
+ * with s = the attention-weighted bilinear sample of the UNPROJECTED tokens and beta = the sum of the weights that went into it.  The
+ * result is what F.linear -> masked_fill -> ocpg_msda_fwd_f32 gives, up to fp32 summation order; value [N, S, M, D] is never formed.
+ *   src [N, S, C] (C = M * D), wv [C, C] (row = output channel), bv [C] or NULL, pad [N, S] bytes (non-zero = padded token) or NULL,
+ *   shapes / level_start / loc / attn as for ocpg_msda_fwd_f32.
+ *   _fwd:        out [N, Lq, C]; s [N, Lq, M, C] and beta [N, Lq, M] are written for the backward.
+ *   _bwd:        grad_src [N, S, C] is ACCUMULATED into by float atomics (the caller zeroes it, as grad_value of ocpg_msda_bwd_f32; NULL =
+ *                not wanted); grad_loc / grad_attn are overwritten.
+ *   _bwd_params: grad_wv [C, C] and grad_bv [C] (NULL = not wanted) from grad_out, s and beta: overwritten, fixed summation order.
+ * Served: C % 64 == 0, C <= 1024, L * P <= 64, S * C < 2^31, naturally aligned buffers; anything else returns -2000 with nothing
+ * launched (alignment included: it is examined before the first launch) and the caller keeps value_proj + ocpg_msda_fwd_f32 / _bwd_f32. */
+int ocpg_msda_sf_fwd_f32(const float* src, const float* wv, const float* bv, const unsigned char* pad,
+                         const int64_t* shapes, const int64_t* level_start, const float* loc, const float* attn,
+                         int N, int S, int M, int D, int L, int Lq, int P,
+                         float* out, float* s, float* beta, void* stream);
+int ocpg_msda_sf_bwd_f32(const float* src, const float* wv, const float* bv, const unsigned char* pad,
+                         const int64_t* shapes, const int64_t* level_start, const float* loc, const float* attn,
+                         const float* grad_out, int N, int S, int M, int D, int L, int Lq, int P,
+                         float* grad_src, float* grad_loc, float* grad_attn, void* stream);
+int ocpg_msda_sf_bwd_params_f32(const float* grad_out, const float* s, const float* beta, int N, int M, int D, int Lq,
+                                float* grad_wv, float* grad_bv, void* stream);
+
 /* MSDeformAttn with 16-BIT STORAGE of value / out / grad_out (opt-in; the reference's op is fp32 / fp64 only, so these entry points
  * have no counterpart there and the parity statement does not cover them).
  *   dtype: 1 = bfloat16, 2 = float16 (the numbering of ocpg_bn_act_*: 0 would be float32 -- use the _f32 entry points); any other

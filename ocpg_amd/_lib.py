@@ -27,6 +27,9 @@ SIGNATURES = {
     "ocpg_msda_bwd_value_sel_f32": [_vp, _vp, _vp] + [_int] * 7 + [_vp, _vp, _vp, _vp],
     "ocpg_msda_bwd_locattn_f32": [_vp, _i64p, _i64p, _vp, _vp, _vp] + [_int] * 7 + [_vp, _vp, _vp],
     "ocpg_msda_bwd_f64": [_vp, _i64p, _i64p, _vp, _vp, _vp] + [_int] * 7 + [_vp, _vp, _vp, _vp],
+    "ocpg_msda_sf_fwd_f32": [_vp, _vp, _vp, _vp, _i64p, _i64p, _vp, _vp] + [_int] * 7 + [_vp, _vp, _vp, _vp],
+    "ocpg_msda_sf_bwd_f32": [_vp, _vp, _vp, _vp, _i64p, _i64p, _vp, _vp, _vp] + [_int] * 7 + [_vp, _vp, _vp, _vp],
+    "ocpg_msda_sf_bwd_params_f32": [_vp, _vp, _vp] + [_int] * 4 + [_vp, _vp, _vp],
     "ocpg_msda_fwd_h16": [_vp, _i64p, _i64p, _vp, _vp] + [_int] * 7 + [_vp, _vp, _int, _vp],
     "ocpg_msda_bwd_h16": [_vp, _i64p, _i64p, _vp, _vp, _vp] + [_int] * 7 + [_vp, _vp, _vp, _vp, _vp, _int, _vp],
     "ocpg_msda_bwd_value_h16": [_vp, _vp, _vp] + [_int] * 7 + [_vp, _vp, _vp, _int, _vp],

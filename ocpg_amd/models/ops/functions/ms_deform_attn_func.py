@@ -325,3 +325,121 @@ class MSDeformAttnFusedFunction(Function):
             else:
                 check(rc, "ocpg_msda_fused_bwd_h16")
         return grad_value.to(value.dtype), None, None, grad_q, None, None, None, None
+
+
+class MSDeformAttnSampleFirstFunction(Function):
+    """value_proj + padding fill + the op for calls with FEW queries (cross-attention), float32: the attention-weighted bilinear sample is
+    taken from the UNPROJECTED tokens and only the N*Lq*M sampled rows are projected (include/ocpg_hip.h: ocpg_msda_sf_*;
+    csrc/msda_sample_first.hip).  Same result as MSDeformAttnFunction on masked_fill(F.linear(src, wv, bv), pad, 0) up to fp32 summation
+    order, without the [N*S, C] x [C, C] GEMM, its two backward GEMMs and the dense grad_value.
+
+    apply(src [N,S,C], wv [C,C], bv [C] | None, pad [N,S] bool | None, shapes, level_start, loc [N,Lq,M,L,P,2], attn [N,Lq,M,L,P]) -> out [N,Lq,C]
+    `supported()` says whether the kernels serve a call; an unserved call raises here (the module asks first and keeps its old path)."""
+
+    @staticmethod
+    def supported(src, wv, bv, loc, attn):
+        if not (src.is_cuda and src.dtype == wv.dtype == loc.dtype == attn.dtype == torch.float32 and (bv is None or bv.dtype == torch.float32)):
+            return False
+        N, S, C = src.shape
+        _, Lq, M, L, P, _ = loc.shape
+        return C % M == 0 and C % 64 == 0 and C <= 1024 and L * P <= 64 and S * C < 2 ** 31 and N * Lq * M < 2 ** 31
+
+    @staticmethod
+    def forward(ctx, src, wv, bv, pad, shapes, level_start, loc, attn):
+        for n, t in (("src", src), ("wv", wv), ("shapes", shapes), ("level_start", level_start), ("loc", loc), ("attn", attn)):
+            require_gpu(n, t)
+        if shapes.dtype != torch.int64 or level_start.dtype != torch.int64:
+            raise RuntimeError("MSDeformAttnSampleFirstFunction: spatial_shapes / level_start_index must be int64")
+        N, S, C = src.shape
+        _, Lq, M, L, P, _ = loc.shape
+        D = C // M
+        src, wv, loc, attn = src.contiguous(), wv.contiguous(), loc.contiguous(), attn.contiguous()
+        bv = None if bv is None else bv.contiguous()
+        if pad is not None:
+            pad = pad.contiguous()
+            pad = pad.view(torch.uint8) if pad.dtype == torch.bool else pad.to(torch.uint8)
+        out = torch.empty((N, Lq, C), dtype=torch.float32, device=src.device)
+        s = torch.empty((N, Lq, M, C), dtype=torch.float32, device=src.device)
+        beta = torch.empty((N, Lq, M), dtype=torch.float32, device=src.device)
+        with torch.cuda.device(src.device), _timed("fwd_dec"):
+            check(lib().ocpg_msda_sf_fwd_f32(src.data_ptr(), wv.data_ptr(), bv.data_ptr() if bv is not None else None,
+                                             pad.data_ptr() if pad is not None else None, shapes.data_ptr(), level_start.data_ptr(),
+                                             loc.data_ptr(), attn.data_ptr(), N, S, M, D, L, Lq, P, out.data_ptr(), s.data_ptr(), beta.data_ptr(),
+                                             stream_ptr()), "ocpg_msda_sf_fwd_f32")
+        ctx.save_for_backward(src, wv, bv, pad, shapes, level_start, loc, attn, s, beta)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        src, wv, bv, pad, shapes, level_start, loc, attn, s, beta = ctx.saved_tensors
+        return _sample_first_backward(ctx, grad_output, src, wv, bv, pad, shapes, level_start, loc, attn, s, beta)
+
+
+def _sample_first_backward(ctx, grad_output, src, wv, bv, pad, shapes, level_start, loc, attn, s, beta):
+    """the backward both sample-first functions share; s / beta None: the forward did not run ocpg_msda_sf_fwd_f32, so they are formed here
+    (one more launch of that kernel, its `out` dropped) when the weight or bias gradient wants them"""
+    N, S, C = src.shape
+    _, Lq, M, L, P, _ = loc.shape
+    D = C // M
+    go = grad_output.contiguous()
+    need_src, need_wv, need_bv = ctx.needs_input_grad[0], ctx.needs_input_grad[1], bv is not None and ctx.needs_input_grad[2]
+    need_loc, need_attn = ctx.needs_input_grad[6], ctx.needs_input_grad[7]
+    grad_src = grad_loc = grad_attn = grad_wv = grad_bv = None
+    p = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    with torch.cuda.device(src.device), _timed("bwd_dec"):
+        if need_src or need_loc or need_attn:
+            grad_src = torch.zeros_like(src) if need_src else None
+            grad_loc, grad_attn = torch.empty_like(loc), torch.empty_like(attn)
+            check(lib().ocpg_msda_sf_bwd_f32(src.data_ptr(), wv.data_ptr(), p(bv), p(pad), shapes.data_ptr(), level_start.data_ptr(),
+                                             loc.data_ptr(), attn.data_ptr(), go.data_ptr(), N, S, M, D, L, Lq, P,
+                                             p(grad_src), grad_loc.data_ptr(), grad_attn.data_ptr(), stream_ptr()), "ocpg_msda_sf_bwd_f32")
+        if need_wv or need_bv:
+            if s is None:
+                out = torch.empty((N, Lq, C), dtype=torch.float32, device=src.device)
+                s = torch.empty((N, Lq, M, C), dtype=torch.float32, device=src.device)
+                beta = torch.empty((N, Lq, M), dtype=torch.float32, device=src.device)
+                check(lib().ocpg_msda_sf_fwd_f32(src.data_ptr(), wv.data_ptr(), p(bv), p(pad), shapes.data_ptr(), level_start.data_ptr(),
+                                                 loc.data_ptr(), attn.data_ptr(), N, S, M, D, L, Lq, P, out.data_ptr(), s.data_ptr(),
+                                                 beta.data_ptr(), stream_ptr()), "ocpg_msda_sf_fwd_f32")
+            grad_wv = torch.empty_like(wv)
+            grad_bv = torch.empty_like(bv) if need_bv else None
+            check(lib().ocpg_msda_sf_bwd_params_f32(go.data_ptr(), s.data_ptr(), beta.data_ptr(), N, M, D, Lq, grad_wv.data_ptr(),
+                                                    p(grad_bv), stream_ptr()), "ocpg_msda_sf_bwd_params_f32")
+    return (grad_src, grad_wv if need_wv else None, grad_bv, None, None, None, grad_loc if need_loc else None,
+            grad_attn if need_attn else None)
+
+
+class MSDeformAttnSampleFirstBackwardFunction(Function):
+    """Same inputs, same result and same gradients as MSDeformAttnSampleFirstFunction, but the FORWARD keeps today's order -- value_proj over
+    all N*S tokens (the module's own Linear routing), the padding fill, ocpg_msda_fwd_f32 -- so `out` has today's bits; `value` is dropped
+    right after (it is not saved), and the backward is the sample-first one: no dense grad_value, none of value_proj's two backward GEMMs.
+    Why: under bf16 autocast a change in the last fp32 bits of the decoder's cross-attention output moves the step's outputs by whole
+    bf16 roundings, so the default keeps them and takes the backward's share of the gain.
+    Call it with gradients enabled (the module does): without them there is no backward to save anything in."""
+
+    supported = staticmethod(MSDeformAttnSampleFirstFunction.supported)
+
+    @staticmethod
+    def forward(ctx, src, wv, bv, pad, shapes, level_start, loc, attn):
+        from ...amp_cache import linear
+        for n, t in (("src", src), ("wv", wv), ("shapes", shapes), ("level_start", level_start), ("loc", loc), ("attn", attn)):
+            require_gpu(n, t)
+        N, S, C = src.shape
+        M = loc.shape[2]
+        src, wv, loc, attn = src.contiguous(), wv.contiguous(), loc.contiguous(), attn.contiguous()
+        bv = None if bv is None else bv.contiguous()
+        with torch.enable_grad():        # the routing of `linear` (which GEMM serves value_proj) looks at the grad mode and at wv.requires_grad
+            value = linear(src.detach(), wv, bv).detach()
+        if pad is not None:
+            value = value.masked_fill(pad[..., None], 0.0)
+            pad = pad.contiguous()
+            pad = pad.view(torch.uint8) if pad.dtype == torch.bool else pad.to(torch.uint8)
+        out = ms_deform_attn_forward(value.view(N, S, M, C // M), shapes, level_start, loc, attn)
+        ctx.save_for_backward(src, wv, bv, pad, shapes, level_start, loc, attn)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        return _sample_first_backward(ctx, grad_output, *ctx.saved_tensors, None, None)

@@ -17,7 +17,8 @@ from ... import amp_cache
 from ...amp_cache import TokenLinear, linear
 from ....util.misc import memo
 from ..functions import MSDeformAttnFunction
-from ..functions.ms_deform_attn_func import MSDeformAttnFusedFunction
+from ..functions.ms_deform_attn_func import (MSDeformAttnFusedFunction, MSDeformAttnSampleFirstBackwardFunction,
+                                              MSDeformAttnSampleFirstFunction)
 
 
 FUSED_FRONT = os.environ.get("OCPG_MSDA_FUSED_FRONT", "1") != "0"   # A/B switch: softmax + location arithmetic (and their backward) inside the op's kernels
@@ -25,6 +26,36 @@ FUSED_FRONT = os.environ.get("OCPG_MSDA_FUSED_FRONT", "1") != "0"   # A/B switch
 # the 16-bit mode's default stays the un-fused op
 FUSED_FRONT_H16 = os.environ.get("OCPG_MSDA_FUSED_FRONT_H16", "0") != "0"
 SELECT_PATH = os.environ.get("OCPG_MSDA_SELECT", "1") != "0"     # A/B switch: per-call choice of the grad_value kernel family (self-attention calls)
+
+
+def sample_first_mode(word):
+    """OCPG_MSDA_SAMPLE_FIRST -> "1" (take the sample-first kernels when `sample_first_wanted` says so), "0" (never) or "force" (whenever
+    the kernels serve the shape); an unknown word raises ValueError."""
+    if word not in ("0", "1", "force"):
+        raise ValueError(f"OCPG_MSDA_SAMPLE_FIRST must be one of '0', '1', 'force', not {word!r}")
+    return word
+
+
+# A/B switch: few-query calls sample the unprojected tokens and project the N*Lq*M sampled rows (csrc/msda_sample_first.hip) instead of
+# projecting all N*S tokens first
+SAMPLE_FIRST = sample_first_mode(os.environ.get("OCPG_MSDA_SAMPLE_FIRST", "1"))
+# A/B switch: whether such a call's FORWARD goes through the sample-first kernel too.  Off by default: the forward then keeps value_proj + op
+# and `out` keeps its bits (only the backward is the sample-first one).  On, the fp32 summation order of `out` changes (1e-7 relative), which
+# under bf16 autocast moves the step's outputs by whole bf16 roundings (measured: DESIGN.md section 4.3c) for another ~70 us per layer
+SAMPLE_FIRST_FWD = os.environ.get("OCPG_MSDA_SAMPLE_FIRST_FWD", "0") != "0"
+# r of sample_first_wanted: the largest measured 4*Lq*L*P / S at which the kernels were still >= 1.3x faster than value_proj + op with cold
+# caches (Lq = 20 at S = 5100: 2.28x; the next point, 0.63, 1.18x -- DESIGN.md section 4.3c, profiles/msda_sample_first_kernel_level.jsonl)
+SAMPLE_FIRST_MAX_RATIO = 0.251
+
+
+def sample_first_wanted(N, S, M, Lq, L, P):
+    """Whether a call of this size is worth taking through the sample-first kernels (a pure host function of the sizes):
+      * not self-attention (Lq == S reads every value);
+      * value_proj is a GEMM over at least amp_cache.TOKEN_LINEAR_MIN_ROWS rows -- below that it is a small GEMM with nothing to win;
+      * the 4 * Lq * L * P token rows a head gathers per image are at most SAMPLE_FIRST_MAX_RATIO of the S rows value_proj would write."""
+    return Lq != S and N * S >= amp_cache.TOKEN_LINEAR_MIN_ROWS and 4 * Lq * L * P <= SAMPLE_FIRST_MAX_RATIO * S
+
+
 MERGED_QUERY_PROJ = True      # A/B switch: sampling_offsets and attention_weights as ONE GEMM over the query (they share their input)
 
 
@@ -133,10 +164,16 @@ class MSDeformAttn(nn.Module):
         else:
             assert (input_spatial_shapes[:, 0] * input_spatial_shapes[:, 1]).sum() == S
 
-        value = self.value_proj(input_flatten) if vd is None else self._linear16(input_flatten, self.value_proj, vd)
-        if input_padding_mask is not None:
-            value = value.masked_fill(input_padding_mask[..., None], 0.0)
-        value = value.view(N, S, M, self.d_model // M)
+        def make_value():
+            value = self.value_proj(input_flatten) if vd is None else self._linear16(input_flatten, self.value_proj, vd)
+            if input_padding_mask is not None:
+                value = value.masked_fill(input_padding_mask[..., None], 0.0)
+            return value.view(N, S, M, self.d_model // M)
+
+        # few queries against many tokens (the decoder's cross-attention): value is not formed at all, see below
+        sample_first = (vd is None and input_flatten.is_cuda and Lq != S
+                        and (SAMPLE_FIRST == "force" or (SAMPLE_FIRST == "1" and sample_first_wanted(N, S, M, Lq, L, P))))
+        value = None if sample_first else make_value()
         if MERGED_QUERY_PROJ and query.is_cuda:
             # One GEMM for both query projections (same input, [256 + 128] output columns): one forward GEMM, one input-gradient
             # GEMM and one weight-gradient GEMM instead of two each plus the add of the two input gradients.  With 2-d reference
@@ -176,6 +213,15 @@ class MSDeformAttn(nn.Module):
         else:
             raise ValueError(f"Last dim of reference_points must be 2 or 4, but get {reference_points.shape[-1]} instead.")
         loc_c = loc.contiguous()
+        if sample_first:
+            vp = self.value_proj
+            # (without gradients there is no backward to save anything in: the forward-keeping form is today's path then)
+            fn = MSDeformAttnSampleFirstFunction if SAMPLE_FIRST_FWD else MSDeformAttnSampleFirstBackwardFunction if torch.is_grad_enabled() else None
+            if fn is not None and fn.supported(input_flatten, vp.weight, vp.bias, loc_c, weights):
+                out = fn.apply(input_flatten, vp.weight, vp.bias, input_padding_mask, input_spatial_shapes, input_level_start_index, loc_c,
+                               weights.contiguous())
+                return self.output_proj(out), loc, weights
+            value = make_value()          # a shape or dtype the kernels do not serve: today's path
         if SELECT_PATH and Lq == S and loc_c.is_cuda:
             loc_c._ocpg_sel = self._sel_state
         out = MSDeformAttnFunction.apply(value.contiguous(), input_spatial_shapes, input_level_start_index,
