@@ -21,7 +21,7 @@
  *     grad_value is ACCUMULATED into (scatter-add): the caller zeroes it first, exactly as
  *     ms_deform_attn_cuda.cu:121 does with at::zeros_like; grad_loc / grad_attn are fully overwritten;
  *   - re-entrant and thread-safe; no global state except the GEMM plan cache above (and, in diagnostic builds only, the
- *     EXP_STAMPS counters).
+ *     EXP_STAMPS counters of the output-tiled MSDeformAttn kernels and of the halo-staged 3x3 convolution).
  *
  * Tensor contract of MSDeformAttn (ms_deform_attn_cuda.cu:28-48):
  *   value        [N, S, M, D]          S = sum_l H_l*W_l
@@ -156,8 +156,8 @@ int ocpg_msda_sf_bwd_params_f32(const float* grad_out, const float* s, const flo
  *   _bwd_h16 is the WHOLE backward for any shape.  shapes_host (may be NULL) and sel_state (may be NULL) as for ocpg_msda_bwd_f32 /
  *   ocpg_msda_bwd_value_sel_f32: with a host copy of the shapes, Lq == S and D in {16, 32} grad_value comes from the column-scatter /
  *   output-tiled kernels (which read grad_out in 16 bits) under the call site's path selection, grad_loc / grad_attn from the gather
- *   row kernel.  Forced paths: OCPG_MSDA_TILE / OCPG_MSDA_COL as documented above; the legacy column variants behind
- *   OCPG_MSDA_COL_LP = 1..3 read fp32 only, so with one of them forced the whole 16-bit backward takes the generic kernel.
+ *   row kernel.  Forced paths: OCPG_MSDA_TILE / OCPG_MSDA_COL as documented above; the single-level column scatter that
+ *   OCPG_MSDA_COL_LP < 4 forces reads fp32 only, so with it forced the whole 16-bit backward takes the generic kernel.
  *   shapes_host of _fwd_h16 is accepted for symmetry and not read.
  *   The fused front end has a 16-bit form of its own: ocpg_msda_fused_fwd_h16 / ocpg_msda_fused_bwd_qproj_h16 below. */
 int ocpg_msda_fwd_h16(const void* value, const int64_t* shapes, const int64_t* level_start,

@@ -18,7 +18,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["-O3", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # gemm.hip plans GEMMs through hipBLASLt (soname libhipblaslt.so.1: inside a torch process the copy torch already loaded)
 LINK = ["-L/opt/rocm/lib", "-lhipblaslt"]
-EXTRA = os.environ.get("OCPG_HIPCC_FLAGS", "").split()     # experiment switches (-DEXP_...)
+EXTRA = os.environ.get("OCPG_HIPCC_FLAGS", "").split()     # extra flags for diagnostic builds (-D switches)
 
 
 def sources():

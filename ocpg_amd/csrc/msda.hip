@@ -703,12 +703,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSDA_WPE, 8
                 if (px >= 0 && px < ww && py >= 0 && py < wh) {      // inside the privatised window: ds_add_f32
                   const int pp = py * ww + px;
                   double* gl_ = acc + pp * D + j;                     // bank-group swizzle: channel group i sits in slot (i+pp)&3
-#ifndef EXP_NO_LDS_ATOMIC
 #pragma unroll
                   for (int c = 0; c < 4; ++c) atomicAdd(gl_ + ((c + pp) & 3) * G, (double)(w[k] * gs[c] * a));   // ds_add_f64
-#else
-                  asm volatile("" ::"v"(gl_), "v"(w[k] * gs[0] * a));
-#endif
                 } else {                                              // outside: straight to memory
                   float* g = gvalue_l + rec[i].off00 + offs[k] + j;
 #pragma unroll
@@ -759,9 +755,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSDA_WPE, 8
         if (v != 0.f) {
           const int pp = i / D, slot = (i % D) / G, jj = i % G;
           const int c = jj + G * ((slot - pp) & 3);                  // undo the bank-group swizzle
-#ifndef EXP_NO_FLUSH
           atomicAdd(gl + ((long long)(oy + pp / ww) * W + ox + pp % ww) * MD + c, v);
-#endif
         }
       }
       __syncthreads();
@@ -1144,7 +1138,7 @@ int ocpg_msda_bwd_value_f32(const float* loc, const float* attn, const float* gr
 }
 
 // grad_value with per-call path selection (include/ocpg_hip.h).  Both paths' kernels are launched; the call site's state decides on the
-// device which of them runs (csrc/msda_col.h).  Shapes, or forced paths (OCPG_MSDA_TILE / OCPG_MSDA_COL / OCPG_MSDA_COL_LP), that do not
+// device which of them runs (csrc/msda_col.h).  Shapes, or forced paths (OCPG_MSDA_TILE / OCPG_MSDA_COL / OCPG_MSDA_COL_LP < 4), that do not
 // allow the choice take the plain entry point's route and leave the state untouched.
 int ocpg_msda_bwd_value_sel_f32(const float* loc, const float* attn, const float* grad_out, int N, int S, int M, int D, int L, int Lq, int P,
                                 float* grad_value, const int64_t* shapes_host, int* sel_state, void* stream) {

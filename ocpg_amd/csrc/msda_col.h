@@ -58,13 +58,17 @@ __device__ __forceinline__ void sel_report(int* sel, int far, int total) {
 // to_tile_pct percent far samples, the tiled family back below to_col_pct), which becomes current
 void select_commit(int* sel, int to_tile_pct, int to_col_pct, hipStream_t st);
 
-// true: the one-pass patch kernel (the only column kernel that takes part in the selection) serves this geometry
+// OCPG_MSDA_COL_LP, read per call: unset or >= 4 = the one-pass patch kernel (k_scatter_col4) may run; anything lower forces the
+// single-level kernel (k_scatter_col), which reads an fp32 grad_out only
+bool patch_kernel_allowed();
+
+// true: the one-pass patch kernel (the only column kernel that takes part in the selection) is allowed and serves this geometry
 bool select_supported(const ColGeom& g, int D, int P);
 
 // Each returns 1 (2: the launched kernel honours `sel`) when it launched, 0 when the shape is not supported (nothing launched).
 int fwd_col(const float* value, const float* loc, const float* attn, int N, int S, int M, int D, int P, const ColGeom& g,
             float* out, hipStream_t st);
-// go_dtype: storage of gout (0 = float32, 1 = bfloat16, 2 = float16); the 16-bit forms are served by the default one-pass kernel only
+// go_dtype: storage of gout (0 = float32, 1 = bfloat16, 2 = float16); the 16-bit forms are served by the one-pass patch kernel only
 int bwd_scatter_col(const float* loc, const float* attn, const void* gout, int N, int S, int M, int D, int P, const ColGeom& g,
                     float* gvalue, hipStream_t st, int* sel = nullptr, int to_tile_pct = 0, int go_dtype = 0);
 

@@ -21,6 +21,7 @@
 #include <cstdlib>
 
 #include "../../include/ocpg_hip.h"
+#include "msda_col.h"
 #include "msda_dev.h"
 #include "msda_host.h"
 
@@ -756,9 +757,8 @@ int bwd_h16(const H* value, const int64_t* shapes, const int64_t* level_start, c
             int N, int S, int M, int D, int L, int Lq, int P, float* grad_value, float* grad_loc, float* grad_attn,
             const int64_t* shapes_host, int* sel_state, int go_dtype, hipStream_t st) {
   const long long rows = (long long)N * Lq * M;
-  // a legacy column-scatter variant forced by OCPG_MSDA_COL_LP = 1..3 reads fp32 only: the whole backward takes the generic kernel then
-  const char* lp = std::getenv("OCPG_MSDA_COL_LP");
-  const bool legacy_forced = lp && std::atoi(lp) < 4;
+  // the single-level column scatter forced by OCPG_MSDA_COL_LP < 4 reads fp32 only: the whole backward takes the generic kernel then
+  const bool legacy_forced = !ocpg_col::patch_kernel_allowed();
   const size_t rec_bytes = (size_t)L * P * sizeof(SampleRec);
   const int G = pow2_group(D, 4);
   if (!legacy_forced && G && (256 / G) * rec_bytes <= 48 * 1024 && fast_ok(S, M, D, L, value, grad_out, grad_out)) {

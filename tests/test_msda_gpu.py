@@ -231,7 +231,7 @@ def test_self_attention_kernels_vs_c_oracle(dev, shapes_l):
     dv, dl, da, dg = (t.to(dev) for t in (value, loc, attn, go))
     ds, dls = shapes.to(dev), ls.to(dev)
     ds._ocpg_host = shapes
-    for env in ({}, {"OCPG_MSDA_COL_LP": "2"}, {"OCPG_MSDA_COL_LP": "1"}, {"OCPG_MSDA_TILE": "1"}, {"OCPG_MSDA_FWD": "col"}, {"OCPG_MSDA_COL": "0"}):
+    for env in ({}, {"OCPG_MSDA_COL_LP": "1"}, {"OCPG_MSDA_TILE": "1"}, {"OCPG_MSDA_FWD": "col"}, {"OCPG_MSDA_COL": "0"}):
         with _env(**env):
             out = ms_deform_attn_forward(dv, ds, dls, dl, da)
             gv, gl, ga = ms_deform_attn_backward(dv, ds, dls, dl, da, dg)
@@ -241,6 +241,27 @@ def test_self_attention_kernels_vs_c_oracle(dev, shapes_l):
         # shows at ~2e-6 of the largest element (the round-1 kernels and the C oracle differ by the same amount)
         assert (gl.cpu() - ogl).abs().max() <= 2e-5 * ogl.abs().max(), env
         assert torch.allclose(ga.cpu(), oga, rtol=1e-3, atol=1e-4), env
+
+
+@pytest.mark.parametrize("D,P", [(16, 4), (32, 2)], ids=["D16_P4", "D32_P2"])
+def test_single_level_scatter_by_dispatch_vs_c_oracle(dev, D, P):
+    """Shapes the one-pass patch kernel does not take (it is D = 32, P = 4 only) reach the single-level column scatter
+    `k_scatter_col<G, 768>` by dispatch, with no environment override: forward + backward element-wise against the C oracle,
+    at the tolerances of test_self_attention_kernels_vs_c_oracle."""
+    from oracle import msda as om
+    from ocpg_amd.models.ops.functions import ms_deform_attn_backward, ms_deform_attn_forward
+    value, shapes, ls, loc, attn, go = _local_inputs(dev, 1, [(16, 24), (8, 12)], M=4, D=D, P=P)
+    oc = om.msda_c_forward(value, shapes, ls, loc, attn)
+    ogv, ogl, oga = om.msda_c_backward(value, shapes, ls, loc, attn, go)
+    dv, dl, da, dg = (t.to(dev) for t in (value, loc, attn, go))
+    ds, dls = shapes.to(dev), ls.to(dev)
+    ds._ocpg_host = shapes
+    out = ms_deform_attn_forward(dv, ds, dls, dl, da)
+    gv, gl, ga = ms_deform_attn_backward(dv, ds, dls, dl, da, dg)
+    assert torch.allclose(out.cpu(), oc, rtol=1e-4, atol=1e-5)
+    assert torch.allclose(gv.cpu(), ogv, rtol=1e-3, atol=1e-4)
+    assert (gl.cpu() - ogl).abs().max() <= 2e-5 * ogl.abs().max()
+    assert torch.allclose(ga.cpu(), oga, rtol=1e-3, atol=1e-4)
 
 
 def test_self_attention_backward_paths_agree_at_bench_size(dev):

@@ -142,10 +142,10 @@ def _run_case(dev, value, shapes, ls, loc, attn, go, dtype, envs, host_shapes, w
 @pytest.mark.parametrize("name", list(SELF_SHAPES))
 def test_self_attention_shapes_vs_c_oracle(dev, dtype, name):
     """Forward and backward at the four self-attention shapes of test_msda_gpu.py, one frame, under the default route (column scatter +
-    row gather), the output-tiled grad_value kernels, the row kernel with atomic scatter (OCPG_MSDA_COL=0) and the generic backward a
-    forced legacy column variant falls to (OCPG_MSDA_COL_LP=2)."""
+    row gather), the output-tiled grad_value kernels, the row kernel with atomic scatter (OCPG_MSDA_COL=0) and the generic backward the
+    forced single-level column scatter, which reads fp32 only, falls to (OCPG_MSDA_COL_LP=1)."""
     value, shapes, ls, loc, attn, go = _local_inputs(1, SELF_SHAPES[name], dtype)
-    _run_case(dev, value, shapes, ls, loc, attn, go, dtype, ({}, {"OCPG_MSDA_TILE": "1"}, {"OCPG_MSDA_COL": "0"}, {"OCPG_MSDA_COL_LP": "2"}),
+    _run_case(dev, value, shapes, ls, loc, attn, go, dtype, ({}, {"OCPG_MSDA_TILE": "1"}, {"OCPG_MSDA_COL": "0"}, {"OCPG_MSDA_COL_LP": "1"}),
               True, name)
 
 
