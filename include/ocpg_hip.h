@@ -563,6 +563,22 @@ int ocpg_attn_smallk_bwd(const void* q, long long ldq, const void* k, long long 
                          int B, int H, int hd, int Lk, float pdrop, unsigned long long seed, unsigned long long offset,
                          const unsigned long long* rng_base, void* dq, long long lddq, float* dk, float* dv, int dtype, void* stream);
 
+/* The same attention for LONGER key sequences (1 <= Lk <= 128; meant for 33..128, head_dim 32, H <= 8 with 256 % H == 0):
+ * csrc/attn_longk.hip walks the keys in chunks of 32 restaged in LDS.  Arguments, layouts, dropout and return codes as for
+ * ocpg_attn_smallk_*, except that the dropout stream is indexed (row * H + head) * 128 + key, and that the backward also takes the
+ * forward's output `out` (row stride ldout): D = sum_j p~_j dp~_j = dout . out, so one sweep over the keys of a 64-key window suffices;
+ * for Lk > 64 the backward is two launches, the second reading and rewriting the dq the first wrote (a 16-bit dq is rounded twice).
+ * Lk < 1: -1006;  Lk > 128, hd != 32, H > 8, 256 % H != 0 or B > 65535: -2000 before any HIP call;  Lq == 0 or B == 0: 0. */
+int ocpg_attn_longk_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv,
+                        const unsigned char* key_pad, float scale, int Lq, int B, int H, int hd, int Lk, float pdrop,
+                        unsigned long long seed, unsigned long long offset, const unsigned long long* rng_base, void* out,
+                        long long ldo, float* lse, int dtype, void* stream);
+int ocpg_attn_longk_bwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv,
+                        const unsigned char* key_pad, const void* dout, long long ldo, const void* out, long long ldout,
+                        const float* lse, float scale, int Lq, int B, int H, int hd, int Lk, float pdrop, unsigned long long seed,
+                        unsigned long long offset, const unsigned long long* rng_base, void* dq, long long lddq, float* dk, float* dv,
+                        int dtype, void* stream);
+
 /* LFM coefficient branch (models/modules.py:17-19,36-39: `self.fc(self.pool(self.laplace(x)))` with laplace a 3x3 VALID conv): the
  * spatial mean of a convolution is linear in the input, mean conv(x)[co] = b[co] + sum w[co,ci,ky,kx] m[ci,ky,kx] with m the mean
  * of x[ci] over the (h-2)x(w-2) window at offset (ky,kx).  x [planes, h, w] fp32 contiguous -> out [planes, 9] window means

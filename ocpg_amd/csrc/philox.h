@@ -1,4 +1,7 @@
-// Counter-based generator shared by the kernels that apply dropout without storing a mask (fused_ln.hip, attn_smallk.hip).
+// Counter-based generator shared by the kernels that apply dropout without storing a mask (fused_ln.hip, attn_smallk.hip,
+// attn_longk.hip).  Stream index of an attention weight (counter = index / 4, word = index % 4):
+//   attn_smallk.hip: (row * H + head) * 32 + key     (key < 32)
+//   attn_longk.hip:  (row * H + head) * 128 + key    (key < 128; the short-key index would collide from key 32 on)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -9,7 +9,8 @@ from . import amp_cache, fallbacks
 from .amp_cache import lookup
 from .ops.functions import attn_smallk_func
 
-HIP_SMALLK = True       # A/B switch: csrc/attn_smallk.hip for the short-key shapes (text gate, decoder self-attention)
+HIP_SMALLK = True       # A/B switch: the own attention kernels (csrc/attn_smallk.hip up to 32 keys, csrc/attn_longk.hip past them) for the
+                        # text gate and the decoder's self-attention; off = the library path for every key count
 
 
 class MultiheadAttention(nn.Module):
@@ -29,7 +30,8 @@ class MultiheadAttention(nn.Module):
         call (the caller then takes forward() on the token-major layout).  Same arithmetic per token as forward()."""
         B, Lq, C = query.shape
         H, hd = self.num_heads, C // self.num_heads
-        if not (HIP_SMALLK and query.is_cuda and hd == 32 and key.shape[0] <= 32 and H <= 8 and not (self.training and self.dropout > 0)):
+        if not (HIP_SMALLK and query.is_cuda and hd == 32 and key.shape[0] <= attn_smallk_func.key_limit() and H <= 8
+                and not (self.training and self.dropout > 0)):
             return None
         w, b = lookup(self.in_proj_weight), lookup(self.in_proj_bias)
         wq, wk, wv = w.chunk(3)
@@ -44,9 +46,9 @@ class MultiheadAttention(nn.Module):
         Lk = key.shape[0]
         H, hd = self.num_heads, C // self.num_heads
         w, b = lookup(self.in_proj_weight), lookup(self.in_proj_bias)
-        if HIP_SMALLK and query.is_cuda and hd == 32 and Lk <= 32 and H <= 8:
+        if HIP_SMALLK and query.is_cuda and hd == 32 and Lk <= attn_smallk_func.key_limit() and H <= 8:
             # short key sequence: the attention core is one HIP kernel each way on the projections' own [L, B, C] layout
-            # (no head permutes, no additive-mask tensor, no flash-attention launch for <= 32 keys)
+            # (no head permutes, no additive-mask tensor, no flash-attention launch; past 32 keys csrc/attn_longk.hip)
             if query is key:
                 wqk, wv = w.split([2 * C, C])
                 bqk, bv = b.split([2 * C, C])
@@ -60,8 +62,8 @@ class MultiheadAttention(nn.Module):
             o = attn_smallk_func.attention(q, k, v, key_padding_mask, hd ** -0.5, H, self.dropout if self.training else 0.0)
             if o is not None:
                 return self.out_proj(o)
-        fallbacks.note("MultiheadAttention", f"head_dim {hd}, {H} heads, {Lk} keys not served by csrc/attn_smallk.hip"
-                       if not (hd == 32 and Lk <= 32 and H <= 8) else "attn_smallk declined the call", query)
+        fallbacks.note("MultiheadAttention", f"head_dim {hd}, {H} heads, {Lk} keys not served by csrc/attn_smallk.hip / attn_longk.hip"
+                       if not (hd == 32 and Lk <= attn_smallk_func.key_limit() and H <= 8) else "attn_smallk declined the call", query)
         # split the packed projection ONCE (backward: one cat per parameter, not three zero-fill + copy + add chains)
         if query is key:        # decoder self-attention: q and k from the same input -> one GEMM
             wqk, wv = w.split([2 * C, C])

@@ -1,9 +1,10 @@
 """Accounting of every place where the product leaves its hand-written HIP kernels for a library path ON A GPU.
 
-The HIP kernels serve the shapes of the BASELINE configurations (head_dim 32, <= 32 text keys, ...).  Other shapes run a
-library kernel (torch SDPA): correct, but not the native path -- so it must never happen silently.  `note()` counts the
-event, warns once per (site, reason) and raises under OCPG_STRICT_HIP=1 (the -m gpu parity tests of the head_dim-32 fixtures
-and bench.py's config-#2 run set it / report the counts).  CPU tensors (host-logic unit tests) are not counted.
+The HIP kernels serve the shapes of the BASELINE configurations (head_dim 32, ...) and captions of up to
+attn_smallk_func.MAX_KEYS text keys.  Other shapes run a library kernel (torch SDPA): correct, but not the native path --
+so it must never happen silently.  `note()` counts the event, warns once per (site, reason) and raises under
+OCPG_STRICT_HIP=1 (the -m gpu parity tests of the head_dim-32 fixtures and bench.py's config-#2 run set it / report the
+counts).  CPU tensors (host-logic unit tests) are not counted.
 """
 import os
 import warnings
