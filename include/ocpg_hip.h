@@ -452,6 +452,12 @@ int ocpg_matcher_cost_f32(const float* logits, const float* boxes, const float* 
  *     between replays (every replay then draws fresh masks, as models/deformable_transformer.py:236-257 does every step);
  *     bwd: gx (x's dtype, may be NULL), gres (may be NULL) fully written; dgb_part [slots, 2, C] partial (dgamma, dbeta) sums,
  *     fully written, slots = ocpg_dropout_add_ln_bwd_slots(R); the caller sums over the slots.
+ *     The _ex symbols are the same kernels with more ports (with every extra absent and g0 fp32: the un-suffixed kernels, bit for bit).
+ *     fwd_ex: addend + y_add (both or neither, fp32 [R,C]): y_add = y + addend, one fp32 add of the value stored as y; y_lp (may be
+ *     NULL): y rounded to nearest even to lp_dtype (1 bf16 / 2 fp16).  bwd_ex: gy = (g0 + g1) + g2 in that order, each addend [R,C] of
+ *     its own dtype (0 / 1 / 2) widened to fp32 first, g1 / g2 may be NULL; gxsum_part (may be NULL) [slots, C]: per slot, the column
+ *     sums of gx as stored (rounded to x's dtype, then widened) -- the bias gradient of the Linear that produced x, summed over the
+ *     slots by the caller.
  *   h = dropout(relu(a + bias)):  a, bias, h share dtype (0 fp32 / 1 bf16), h may alias a; bwd from h only:
  *     ga = gh / (1-p) where h > 0; dbias_part [slots, C] fp32 partial column sums, fully written, slots =
  *     ocpg_bias_relu_dropout_bwd_slots(R, C, dtype); the caller sums over the slots. */
@@ -462,6 +468,13 @@ int ocpg_dropout_add_ln_bwd(const float* gy, const void* x, const float* res, co
                             long long R, int C, float p, unsigned long long seed, unsigned long long offset, const unsigned long long* rng_base,
                             int x_dtype, void* gx, float* gres, float* dgb_part, void* stream);
 long long ocpg_dropout_add_ln_bwd_slots(long long R);
+int ocpg_dropout_add_ln_fwd_ex(const void* x, const float* res, const float* gamma, const float* beta, long long R, int C, float eps, float p,
+                               unsigned long long seed, unsigned long long offset, const unsigned long long* rng_base, int x_dtype, float* y,
+                               float* mean, float* rstd, const float* addend, float* y_add, void* y_lp, int lp_dtype, void* stream);
+int ocpg_dropout_add_ln_bwd_ex(const void* g0, int g0_dtype, const void* g1, int g1_dtype, const void* g2, int g2_dtype, const void* x,
+                               const float* res, const float* gamma, const float* mean, const float* rstd, long long R, int C, float p,
+                               unsigned long long seed, unsigned long long offset, const unsigned long long* rng_base, int x_dtype, void* gx,
+                               float* gres, float* dgb_part, float* gxsum_part, void* stream);
 int ocpg_bias_relu_dropout_fwd(const void* a, const void* bias, long long R, int C, float p, unsigned long long seed,
                                unsigned long long offset, const unsigned long long* rng_base, int dtype, void* h, void* stream);
 int ocpg_bias_relu_dropout_bwd(const void* gh, const void* h, long long R, int C, float p, int dtype, void* ga, float* dbias_part,

@@ -109,6 +109,10 @@ SIGNATURES = {
                                + [_vp] * 4,
     "ocpg_dropout_add_ln_bwd": [_vp] * 6 + [ctypes.c_longlong, _int, ctypes.c_float, ctypes.c_ulonglong, ctypes.c_ulonglong, _vp, _int] + [_vp] * 4,
     "ocpg_dropout_add_ln_bwd_slots": [ctypes.c_longlong],
+    "ocpg_dropout_add_ln_fwd_ex": [_vp] * 4 + [ctypes.c_longlong, _int, ctypes.c_float, ctypes.c_float, ctypes.c_ulonglong, ctypes.c_ulonglong, _vp, _int]
+                                  + [_vp] * 6 + [_int, _vp],
+    "ocpg_dropout_add_ln_bwd_ex": [_vp, _int] * 3 + [_vp] * 5 + [ctypes.c_longlong, _int, ctypes.c_float, ctypes.c_ulonglong, ctypes.c_ulonglong, _vp, _int]
+                                  + [_vp] * 5,
     "ocpg_bias_relu_dropout_fwd": [_vp, _vp, ctypes.c_longlong, _int, ctypes.c_float, ctypes.c_ulonglong, ctypes.c_ulonglong, _vp, _int, _vp, _vp],
     "ocpg_bias_relu_dropout_bwd": [_vp, _vp, ctypes.c_longlong, _int, ctypes.c_float, _int, _vp, _vp, _vp],
     "ocpg_bias_relu_dropout_bwd_slots": [ctypes.c_longlong, _int, _int],
@@ -188,7 +192,9 @@ def collect_kernel_timing(work=None):
 CENSUS = {"on": False, "calls": {}}
 # a symbol that is another ROW ORDER of a kernel (same arguments, bit-identical result) is also counted as the symbol it stands in for:
 # the census answers "which kernel family served this module", and that answer does not change with the row order
-CENSUS_ALSO = {"ocpg_conv3x3_mfma_dgrad_w_s2": "ocpg_conv3x3_mfma_dgrad_w", "ocpg_conv3x3_mfma_dgrad_w_s2_h16": "ocpg_conv3x3_mfma_dgrad_w_h16"}
+CENSUS_ALSO = {"ocpg_conv3x3_mfma_dgrad_w_s2": "ocpg_conv3x3_mfma_dgrad_w", "ocpg_conv3x3_mfma_dgrad_w_s2_h16": "ocpg_conv3x3_mfma_dgrad_w_h16",
+               # the same dropout+add+LayerNorm kernels with more ports (csrc/fused_ln.hip)
+               "ocpg_dropout_add_ln_fwd_ex": "ocpg_dropout_add_ln_fwd", "ocpg_dropout_add_ln_bwd_ex": "ocpg_dropout_add_ln_bwd"}
 
 
 def census(on=True):

@@ -38,35 +38,38 @@ template <> struct IO<float> {
   static __device__ __forceinline__ void store4(float* p, const float (&f)[4]) { *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]); }
 };
 template <> struct IO<__hip_bfloat16> {
-  static __device__ __forceinline__ void load4(const __hip_bfloat16* p, float (&f)[4]) {
-    const uint2 v = *reinterpret_cast<const uint2*>(p);
+  // four values <-> their two packed 32-bit words (what store4 writes / load4 reads)
+  static __device__ __forceinline__ void unpack4(const uint2 v, float (&f)[4]) {
     f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u); f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
   }
-  static __device__ __forceinline__ void store4(__hip_bfloat16* p, const float (&f)[4]) {
+  static __device__ __forceinline__ uint2 pack4(const float (&f)[4]) {
     uint32_t w[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const __hip_bfloat16 lo = __float2bfloat16(f[2 * i]), hi = __float2bfloat16(f[2 * i + 1]);
       w[i] = (uint32_t)(*reinterpret_cast<const uint16_t*>(&lo)) | ((uint32_t)(*reinterpret_cast<const uint16_t*>(&hi)) << 16);
     }
-    *reinterpret_cast<uint2*>(p) = make_uint2(w[0], w[1]);
+    return make_uint2(w[0], w[1]);
   }
+  static __device__ __forceinline__ void load4(const __hip_bfloat16* p, float (&f)[4]) { unpack4(*reinterpret_cast<const uint2*>(p), f); }
+  static __device__ __forceinline__ void store4(__hip_bfloat16* p, const float (&f)[4]) { *reinterpret_cast<uint2*>(p) = pack4(f); }
 };
 
 template <> struct IO<__half> {          // fp16 storage (round 4: the reference's --amp dtype, BASELINE config #5)
-  static __device__ __forceinline__ void load4(const __half* p, float (&f)[4]) {
-    const uint2 v = *reinterpret_cast<const uint2*>(p);
+  static __device__ __forceinline__ void unpack4(const uint2 v, float (&f)[4]) {
     const __half2 a = *reinterpret_cast<const __half2*>(&v.x), b = *reinterpret_cast<const __half2*>(&v.y);
     const float2 fa = __half22float2(a), fb = __half22float2(b);
     f[0] = fa.x; f[1] = fa.y; f[2] = fb.x; f[3] = fb.y;
   }
-  static __device__ __forceinline__ void store4(__half* p, const float (&f)[4]) {
+  static __device__ __forceinline__ uint2 pack4(const float (&f)[4]) {
     const __half2 a = __floats2half2_rn(f[0], f[1]), b = __floats2half2_rn(f[2], f[3]);
     uint2 v;
     v.x = *reinterpret_cast<const uint32_t*>(&a);
     v.y = *reinterpret_cast<const uint32_t*>(&b);
-    *reinterpret_cast<uint2*>(p) = v;
+    return v;
   }
+  static __device__ __forceinline__ void load4(const __half* p, float (&f)[4]) { unpack4(*reinterpret_cast<const uint2*>(p), f); }
+  static __device__ __forceinline__ void store4(__half* p, const float (&f)[4]) { *reinterpret_cast<uint2*>(p) = pack4(f); }
 };
 
 __device__ __forceinline__ float wave_sum_all(float v) {
@@ -77,12 +80,23 @@ __device__ __forceinline__ float wave_sum_all(float v) {
 
 constexpr int NCH_MAX = 8;      // float4 chunks per lane: C <= 64 * 4 * NCH_MAX = 2048
 
+// 16-bit -> fp32 loads / fp32 -> 16-bit stores of the extra ports, dtype chosen at run time (uniform): 0 fp32, 1 bf16, 2 fp16
+__device__ __forceinline__ void load4_dt(const void* p, int dt, long long idx, float (&f)[4]) {
+  if (dt == 0) IO<float>::load4((const float*)p + idx, f);
+  else if (dt == 1) IO<__hip_bfloat16>::load4((const __hip_bfloat16*)p + idx, f);
+  else IO<__half>::load4((const __half*)p + idx, f);
+}
+// extra output ports of dal_fwd (EX instantiations only): y_add = y + addend (fp32), y_lp = y rounded to bf16 (lp_dtype 1) / fp16 (2)
+struct FwdPorts { const float* addend; float* y_add; void* y_lp; int lp_dtype; };
+// extra ports of dal_bwd (EX instantiations only): gy = (g0 + g1) + g2 with per-addend dtypes; gxsum [slots, C] partial column sums of gx
+struct BwdPorts { const void* g1; const void* g2; int dt0, dt1, dt2; float* gxsum; };
+
 // y = LN(res + dropout(x)) ; one wave per row
-template <typename XT, int NCH>
+template <typename XT, int NCH, bool EX>
 __global__ __launch_bounds__(256) void dal_fwd(const XT* __restrict__ x, const float* __restrict__ res, const float* __restrict__ gamma,
                                                const float* __restrict__ beta, long long R, int C, float eps, uint32_t thr, float scale,
                                                uint64_t seed, uint64_t offset0, const uint64_t* __restrict__ rng_base,
-                                               float* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd) {
+                                               float* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd, FwdPorts ex) {
   const uint64_t offset = offset0 + (rng_base ? *rng_base : 0ull);      // graph replays: the step's base lives in device memory
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= R) return;
@@ -120,22 +134,44 @@ __global__ __launch_bounds__(256) void dal_fwd(const XT* __restrict__ x, const f
 #pragma unroll
       for (int j = 0; j < 4; ++j) o[j] = (z[i][j] - mu) * rs * g[j] + b[j];
       IO<float>::store4(y + row * C + 4 * ch, o);
+      if constexpr (EX) {                   // the ports read the registers `y` was stored from: writes only
+        if (ex.y_add) {
+          float ad[4], q[4];
+          IO<float>::load4(ex.addend + row * C + 4 * ch, ad);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) q[j] = o[j] + ad[j];
+          IO<float>::store4(ex.y_add + row * C + 4 * ch, q);
+        }
+        if (ex.y_lp) {
+          if (ex.lp_dtype == 1) IO<__hip_bfloat16>::store4((__hip_bfloat16*)ex.y_lp + row * C + 4 * ch, o);
+          else IO<__half>::store4((__half*)ex.y_lp + row * C + 4 * ch, o);
+        }
+      }
     }
   }
   if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
 }
 
 // backward: persistent waves over the rows; gx (XT), gres (fp32), dgamma / dbeta accumulated (caller zeroes them)
-template <typename XT, int NCH>
+template <typename XT, int NCH, bool EX>
 __global__ __launch_bounds__(256) void dal_bwd(const float* __restrict__ gy, const XT* __restrict__ x, const float* __restrict__ res,
                                                const float* __restrict__ gamma, const float* __restrict__ mean,
                                                const float* __restrict__ rstd, long long R, int C, uint32_t thr, float scale, uint64_t seed,
                                                uint64_t offset0, const uint64_t* __restrict__ rng_base, XT* __restrict__ gx,
-                                               float* __restrict__ gres, float* __restrict__ dgamma) {
+                                               float* __restrict__ gres, float* __restrict__ dgamma, BwdPorts ex) {
+  // Every multiply-add below is spelled out (fmaf) and the compiler forms none of its own: which products it would contract depends on
+  // the block structure around them, and the instantiations with and without the extra ports must round alike (the _ex symbols are
+  // bit-identical to the un-suffixed ones on the same gradient)
+#pragma clang fp contract(off)
   const uint64_t offset = offset0 + (rng_base ? *rng_base : 0ull);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nch = C / 4;
   float dg[NCH][4], db[NCH][4], g[NCH][4];
+  float gs[EX ? NCH : 1][4];                // EX: column sums of gx as stored (the bias gradient of the Linear that produced x)
+#pragma unroll
+  for (int i = 0; i < (EX ? NCH : 1); ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) gs[i][j] = 0.f;
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
 #pragma unroll
@@ -153,15 +189,31 @@ __global__ __launch_bounds__(256) void dal_bwd(const float* __restrict__ gy, con
         float xv[4], rv[4], dy[4];
         IO<XT>::load4(x + row * C + 4 * ch, xv);
         IO<float>::load4(res + row * C + 4 * ch, rv);
-        IO<float>::load4(gy + row * C + 4 * ch, dy);
+        if constexpr (EX) {                 // gy = (g0 + g1) + g2, widened to fp32 first (exact)
+          load4_dt(gy, ex.dt0, row * C + 4 * ch, dy);
+          if (ex.g1) {
+            float t[4];
+            load4_dt(ex.g1, ex.dt1, row * C + 4 * ch, t);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dy[j] += t[j];
+          }
+          if (ex.g2) {
+            float t[4];
+            load4_dt(ex.g2, ex.dt2, row * C + 4 * ch, t);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dy[j] += t[j];
+          }
+        } else {
+          IO<float>::load4(gy + row * C + 4 * ch, dy);
+        }
         keep4(seed, offset, (uint64_t)(row * C) / 4 + ch, thr, scale, kk[i]);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          xh[i][j] = (rv[j] + xv[j] * kk[i][j] - mu) * rs;
+          xh[i][j] = (fmaf(xv[j], kk[i][j], rv[j]) - mu) * rs;         // z as the forward kernel rounds it
           a[i][j] = dy[j] * g[i][j];
           s1 += a[i][j];
-          s2 += a[i][j] * xh[i][j];
-          dg[i][j] += dy[j] * xh[i][j];
+          s2 = fmaf(a[i][j], xh[i][j], s2);
+          dg[i][j] = fmaf(dy[j], xh[i][j], dg[i][j]);
           db[i][j] += dy[j];
         }
       }
@@ -174,16 +226,31 @@ __global__ __launch_bounds__(256) void dal_bwd(const float* __restrict__ gy, con
       if (ch < nch) {
         float gz[4], gxv[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { gz[j] = rs * (a[i][j] - s1 - xh[i][j] * s2); gxv[j] = gz[j] * kk[i][j]; }
+        for (int j = 0; j < 4; ++j) { gz[j] = rs * fmaf(-xh[i][j], s2, a[i][j] - s1); gxv[j] = gz[j] * kk[i][j]; }
         if (gres) IO<float>::store4(gres + row * C + 4 * ch, gz);
-        if (gx) IO<XT>::store4(gx + row * C + 4 * ch, gxv);
+        if constexpr (!EX) {
+          if (gx) IO<XT>::store4(gx + row * C + 4 * ch, gxv);
+        } else if constexpr (sizeof(XT) == 4) {
+          if (gx) IO<XT>::store4(gx + row * C + 4 * ch, gxv);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) gs[i][j] += gxv[j];
+        } else {
+          // the column sums take the very words that are stored, widened back: a second rounding of gz * keep next to the store's
+          // could be contracted into one mixed-precision multiply (one rounding instead of two) and leave other bits than the store
+          const uint2 w = IO<XT>::pack4(gxv);
+          float st[4];
+          if (gx) *reinterpret_cast<uint2*>(gx + row * C + 4 * ch) = w;
+          IO<XT>::unpack4(w, st);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) gs[i][j] += st[j];
+        }
       }
     }
   }
   // flush d(gamma), d(beta): reduce the 4 waves of the workgroup through LDS, then ONE plain store per column into this
   // workgroup's row of the partial buffer dgb_part [gridDim.x, 2, C] (the caller sums the rows; same-address float atomics
   // from 1024 workgroups serialise)
-  __shared__ float red[2][4][64 * 4];
+  __shared__ float red[EX ? 3 : 2][4][64 * 4];
   float* part = dgamma + (long long)blockIdx.x * 2 * C;
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
@@ -191,12 +258,19 @@ __global__ __launch_bounds__(256) void dal_bwd(const float* __restrict__ gy, con
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < 4; ++j) { red[0][wave][lane * 4 + j] = dg[i][j]; red[1][wave][lane * 4 + j] = db[i][j]; }
+    if constexpr (EX) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) red[2][wave][lane * 4 + j] = gs[i][j];
+    }
     __syncthreads();
     const int col = threadIdx.x;            // 256 threads <-> the 256 columns of chunk group i
     const int ch = col / 4 + 64 * i;
     if (ch < nch) {
       part[64 * 4 * i + col] = red[0][0][col] + red[0][1][col] + red[0][2][col] + red[0][3][col];
       part[C + 64 * 4 * i + col] = red[1][0][col] + red[1][1][col] + red[1][2][col] + red[1][3][col];
+      if constexpr (EX) {
+        if (ex.gxsum) ex.gxsum[(long long)blockIdx.x * C + 64 * 4 * i + col] = red[2][0][col] + red[2][1][col] + red[2][2][col] + red[2][3][col];
+      }
     }
   }
 }
@@ -297,11 +371,13 @@ inline uint32_t threshold(float p) {
 
 extern "C" {
 
-int ocpg_dropout_add_ln_fwd(const void* x, const float* res, const float* gamma, const float* beta, long long R, int C, float eps, float p,
-                            unsigned long long seed, unsigned long long offset, const unsigned long long* rng_base, int x_dtype, float* y,
-                            float* mean, float* rstd, void* stream) {
+static int dal_fwd_launch(const void* x, const float* res, const float* gamma, const float* beta, long long R, int C, float eps, float p,
+                          unsigned long long seed, unsigned long long offset, const unsigned long long* rng_base, int x_dtype, float* y,
+                          float* mean, float* rstd, const FwdPorts& ex, void* stream) {
   if (R < 0 || C <= 0 || C % 4 != 0 || C > 64 * 4 * NCH_MAX) return -1006;
   if (p < 0.f || p >= 1.f) return -1007;
+  if ((ex.addend != nullptr) != (ex.y_add != nullptr)) return -1011;
+  if (ex.y_lp && ex.lp_dtype != 1 && ex.lp_dtype != 2) return -1008;
   if (R == 0) return 0;
   if (!x || !res || !gamma || !beta) return -1001;
   if (!y || !mean || !rstd) return -1010;
@@ -311,11 +387,25 @@ int ocpg_dropout_add_ln_fwd(const void* x, const float* res, const float* gamma,
   hipStream_t st = (hipStream_t)stream;
   if (x_dtype < 0 || x_dtype > 2) return -1008;
   const int nc = (C + 255) / 256;
-#define DAL_FWD(XT_, N_) dal_fwd<XT_, N_><<<grid, 256, 0, st>>>((const XT_*)x, res, gamma, beta, R, C, eps, thr, scale, seed, offset, (const uint64_t*)rng_base, y, mean, rstd)
-#define DAL_FWD_T(XT_) do { if (nc <= 1) DAL_FWD(XT_, 1); else if (nc <= 2) DAL_FWD(XT_, 2); else if (nc <= 4) DAL_FWD(XT_, 4); else DAL_FWD(XT_, 8); } while (0)
+  const bool extras = ex.y_add || ex.y_lp;          // absent: the plain instantiation, the kernel the un-suffixed symbol always launched
+#define DAL_FWD(XT_, N_, EX_) dal_fwd<XT_, N_, EX_><<<grid, 256, 0, st>>>((const XT_*)x, res, gamma, beta, R, C, eps, thr, scale, seed, offset, (const uint64_t*)rng_base, y, mean, rstd, ex)
+#define DAL_FWD_N(XT_, EX_) do { if (nc <= 1) DAL_FWD(XT_, 1, EX_); else if (nc <= 2) DAL_FWD(XT_, 2, EX_); else if (nc <= 4) DAL_FWD(XT_, 4, EX_); else DAL_FWD(XT_, 8, EX_); } while (0)
+#define DAL_FWD_T(XT_) do { if (extras) DAL_FWD_N(XT_, true); else DAL_FWD_N(XT_, false); } while (0)
   if (x_dtype == 0) DAL_FWD_T(float); else if (x_dtype == 1) DAL_FWD_T(__hip_bfloat16); else DAL_FWD_T(__half);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : -(int)e;
+}
+
+int ocpg_dropout_add_ln_fwd(const void* x, const float* res, const float* gamma, const float* beta, long long R, int C, float eps, float p,
+                            unsigned long long seed, unsigned long long offset, const unsigned long long* rng_base, int x_dtype, float* y,
+                            float* mean, float* rstd, void* stream) {
+  return dal_fwd_launch(x, res, gamma, beta, R, C, eps, p, seed, offset, rng_base, x_dtype, y, mean, rstd, FwdPorts{nullptr, nullptr, nullptr, 0}, stream);
+}
+
+int ocpg_dropout_add_ln_fwd_ex(const void* x, const float* res, const float* gamma, const float* beta, long long R, int C, float eps, float p,
+                               unsigned long long seed, unsigned long long offset, const unsigned long long* rng_base, int x_dtype, float* y,
+                               float* mean, float* rstd, const float* addend, float* y_add, void* y_lp, int lp_dtype, void* stream) {
+  return dal_fwd_launch(x, res, gamma, beta, R, C, eps, p, seed, offset, rng_base, x_dtype, y, mean, rstd, FwdPorts{addend, y_add, y_lp, lp_dtype}, stream);
 }
 
 long long ocpg_dropout_add_ln_bwd_slots(long long R) {
@@ -323,13 +413,14 @@ long long ocpg_dropout_add_ln_bwd_slots(long long R) {
   return want < 1 ? 1 : (want < 1024 ? want : 1024);
 }
 
-int ocpg_dropout_add_ln_bwd(const float* gy, const void* x, const float* res, const float* gamma, const float* mean, const float* rstd,
-                            long long R, int C, float p, unsigned long long seed, unsigned long long offset, const unsigned long long* rng_base,
-                            int x_dtype, void* gx, float* gres, float* dgb_part, void* stream) {
+static int dal_bwd_launch(const void* g0, const void* x, const float* res, const float* gamma, const float* mean, const float* rstd,
+                          long long R, int C, float p, unsigned long long seed, unsigned long long offset, const unsigned long long* rng_base,
+                          int x_dtype, void* gx, float* gres, float* dgb_part, const BwdPorts& ex, void* stream) {
   if (R < 0 || C <= 0 || C % 4 != 0 || C > 64 * 4 * NCH_MAX) return -1006;
   if (p < 0.f || p >= 1.f) return -1007;
+  if (ex.dt0 < 0 || ex.dt0 > 2 || (ex.g1 && (ex.dt1 < 0 || ex.dt1 > 2)) || (ex.g2 && (ex.dt2 < 0 || ex.dt2 > 2))) return -1008;
   if (R == 0) return 0;
-  if (!gy || !x || !res || !gamma || !mean || !rstd) return -1001;
+  if (!g0 || !x || !res || !gamma || !mean || !rstd) return -1001;
   if (!dgb_part) return -1010;
   const uint32_t thr = threshold(p);
   const float scale = 1.f / (1.f - p);
@@ -337,11 +428,28 @@ int ocpg_dropout_add_ln_bwd(const float* gy, const void* x, const float* res, co
   hipStream_t st = (hipStream_t)stream;
   if (x_dtype < 0 || x_dtype > 2) return -1008;
   const int nc = (C + 255) / 256;
-#define DAL_BWD(XT_, N_) dal_bwd<XT_, N_><<<grid, 256, 0, st>>>(gy, (const XT_*)x, res, gamma, mean, rstd, R, C, thr, scale, seed, offset, (const uint64_t*)rng_base, (XT_*)gx, gres, dgb_part)
-#define DAL_BWD_T(XT_) do { if (nc <= 1) DAL_BWD(XT_, 1); else if (nc <= 2) DAL_BWD(XT_, 2); else if (nc <= 4) DAL_BWD(XT_, 4); else DAL_BWD(XT_, 8); } while (0)
+  const bool extras = ex.dt0 != 0 || ex.g1 || ex.g2 || ex.gxsum;
+#define DAL_BWD(XT_, N_, EX_) dal_bwd<XT_, N_, EX_><<<grid, 256, 0, st>>>((const float*)g0, (const XT_*)x, res, gamma, mean, rstd, R, C, thr, scale, seed, offset, (const uint64_t*)rng_base, (XT_*)gx, gres, dgb_part, ex)
+#define DAL_BWD_N(XT_, EX_) do { if (nc <= 1) DAL_BWD(XT_, 1, EX_); else if (nc <= 2) DAL_BWD(XT_, 2, EX_); else if (nc <= 4) DAL_BWD(XT_, 4, EX_); else DAL_BWD(XT_, 8, EX_); } while (0)
+#define DAL_BWD_T(XT_) do { if (extras) DAL_BWD_N(XT_, true); else DAL_BWD_N(XT_, false); } while (0)
   if (x_dtype == 0) DAL_BWD_T(float); else if (x_dtype == 1) DAL_BWD_T(__hip_bfloat16); else DAL_BWD_T(__half);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : -(int)e;
+}
+
+int ocpg_dropout_add_ln_bwd(const float* gy, const void* x, const float* res, const float* gamma, const float* mean, const float* rstd,
+                            long long R, int C, float p, unsigned long long seed, unsigned long long offset, const unsigned long long* rng_base,
+                            int x_dtype, void* gx, float* gres, float* dgb_part, void* stream) {
+  return dal_bwd_launch(gy, x, res, gamma, mean, rstd, R, C, p, seed, offset, rng_base, x_dtype, gx, gres, dgb_part,
+                        BwdPorts{nullptr, nullptr, 0, 0, 0, nullptr}, stream);
+}
+
+int ocpg_dropout_add_ln_bwd_ex(const void* g0, int g0_dtype, const void* g1, int g1_dtype, const void* g2, int g2_dtype, const void* x,
+                               const float* res, const float* gamma, const float* mean, const float* rstd, long long R, int C, float p,
+                               unsigned long long seed, unsigned long long offset, const unsigned long long* rng_base, int x_dtype, void* gx,
+                               float* gres, float* dgb_part, float* gxsum_part, void* stream) {
+  return dal_bwd_launch(g0, x, res, gamma, mean, rstd, R, C, p, seed, offset, rng_base, x_dtype, gx, gres, dgb_part,
+                        BwdPorts{g1, g2, g0_dtype, g1_dtype, g2_dtype, gxsum_part}, stream);
 }
 
 int ocpg_bias_relu_dropout_fwd(const void* a, const void* bias, long long R, int C, float p, unsigned long long seed,

@@ -568,13 +568,31 @@ def linear(x, w, b):
         return SmallLinearFunction.apply(x, w, b)
     if _small_linear_f32_ok(x, w, b):
         return SmallLinearF32Function.apply(x, w, b)
+    ops = _token_linear_operands(x, w, b)
+    if ops is not None:
+        x, w, b = ops
+        return TokenLinearFunction.apply(x.reshape(-1, k), w, b).view(*x.shape[:-1], w.shape[0])
+    return F.linear(x, w, b)
+
+
+def _token_linear_operands(x, w, b):
+    """(x, w, b) in the dtype TokenLinearFunction would run them in, or None when `linear` would not take that path for them."""
+    k = x.shape[-1]
     if SPLIT_K and x.is_cuda and w.requires_grad and x.numel() >= TOKEN_LINEAR_MIN_ROWS * k and torch.is_grad_enabled():
         if torch.is_autocast_enabled("cuda"):
             dt = torch.get_autocast_dtype("cuda")
             x, w, b = x.to(dt), w.to(dt), None if b is None else b.to(dt)
         if x.dtype == w.dtype:
-            return TokenLinearFunction.apply(x.reshape(-1, k), w, b).view(*x.shape[:-1], w.shape[0])
-    return F.linear(x, w, b)
+            return x, w, b
+    return None
+
+
+def token_linear_operands(x, w, b):
+    """The same question for callers that fuse such a Linear with what follows it (Linear + dropout/add/LayerNorm as one autograd
+    node): the operands of the many-row GEMM path, or None when `linear` serves (x, w, b) another way (few-row kernels, F.linear)."""
+    if _small_linear_ok(x, w, b) or _small_linear_f32_ok(x, w, b):
+        return None
+    return _token_linear_operands(x, w, b)
 
 
 class TokenLinear(nn.Linear):

@@ -32,14 +32,50 @@ def _drop_add_norm(x, res, drop, norm):
     return norm(res + drop(x))
 
 
-def _ffn_hidden(src, linear1, activation, drop):
-    """drop(activation(linear1(src))): GEMM + one fused bias/ReLU/dropout pass on the GPU (ReLU FFNs)."""
+def _ports_ok(res, norm):
+    """Whether this norm(res + drop(.)) site may use the extra ports of the fused kernels (fused_ln_func.PORTS)."""
+    c = res.shape[-1]
+    return (fused_ln_func.PORTS and FUSED_GLUE and res.is_cuda and res.dtype == torch.float32 and isinstance(norm, nn.LayerNorm)
+            and norm.elementwise_affine and c % 4 == 0 and c <= 2048)
+
+
+def _ffn_lp_dtype(src, linear1, activation):
+    """The 16-bit dtype `_ffn_hidden` would cast `src` to for its fused GEMM, or None (fp32 runs, other FFNs)."""
+    if FUSED_GLUE and activation is F.relu and src.is_cuda and linear1.bias is not None and torch.is_autocast_enabled("cuda"):
+        dt = torch.get_autocast_dtype("cuda")
+        if dt in (torch.bfloat16, torch.float16) and linear1.weight.shape[0] % 4 == 0:
+            return dt
+    return None
+
+
+def _drop_add_norm_ports(x, res, drop, norm, addend=None, lp_dtype=None):
+    """-> (norm(res + drop(x)), that + addend | None, that in lp_dtype | None) from one fused pass each way."""
+    if fused_ln_func.supported(x, res, x.shape[-1]):
+        return fused_ln_func.dropout_add_layer_norm_ports(x, res, norm, drop.p if drop.training else 0.0, addend, lp_dtype)
+    y = norm(res + drop(x))
+    return y, (None if addend is None else y + addend), None
+
+
+def _linear_drop_add_norm_ports(x, w, b, res, drop, norm, addend=None, lp_dtype=None):
+    """The same for x W^T + b; a Linear over many rows (amp_cache.TokenLinearFunction's GEMMs) and the norm are ONE autograd node whose
+    backward kernel also forms the bias gradient's partial column sums."""
+    ops = amp_cache.token_linear_operands(x, w, b)
+    if ops is not None and ops[0].dtype in (torch.float32, torch.bfloat16, torch.float16) and tuple(x.shape[:-1]) == tuple(res.shape[:-1]) \
+            and w.shape[0] == res.shape[-1]:
+        x2 = ops[0].reshape(-1, x.shape[-1])
+        return fused_ln_func.linear_dropout_add_layer_norm(x2, ops[1], ops[2], res, norm, drop.p if drop.training else 0.0, addend, lp_dtype)
+    return _drop_add_norm_ports(amp_cache.linear(x, w, b), res, drop, norm, addend, lp_dtype)
+
+
+def _ffn_hidden(src, linear1, activation, drop, src_lp=None):
+    """drop(activation(linear1(src))): GEMM + one fused bias/ReLU/dropout pass on the GPU (ReLU FFNs).  src_lp: src already in the
+    autocast dtype (a port of the norm kernel that produced src), used instead of casting src."""
     if FUSED_GLUE and activation is F.relu and src.is_cuda and linear1.bias is not None:
         w, b = amp_cache.lookup(linear1.weight), amp_cache.lookup(linear1.bias)
         x = src
         if torch.is_autocast_enabled("cuda"):
             dt = torch.get_autocast_dtype("cuda")
-            x, w, b = x.to(dt), w.to(dt), b.to(dt)
+            x, w, b = (src_lp if (src_lp is not None and src_lp.dtype == dt) else x.to(dt)), w.to(dt), b.to(dt)
         if x.dtype == w.dtype and x.dtype in (torch.float32, torch.bfloat16, torch.float16) and w.shape[0] % 4 == 0:
             x2 = x.reshape(-1, x.shape[-1])
             splits = amp_cache._split_rows(x2.shape[0]) if amp_cache.SPLIT_K else 1
@@ -86,7 +122,13 @@ class DeformableTransformerEncoderLayer(nn.Module):
         self.dropout3 = nn.Dropout(dropout)
         self.norm2 = nn.LayerNorm(d_model)
 
-    def forward(self, src, pos, reference_points, spatial_shapes, level_start_index, padding_mask=None):
+    def forward(self, src, pos, reference_points, spatial_shapes, level_start_index, padding_mask=None, carry=None):
+        """carry (a dict the encoder hands to its layers in turn, or None): carry["q"] = this layer's query `src + pos`, formed by the
+        previous layer's norm2 kernel; with carry["want"] this layer leaves the next one's there."""
+        if _ports_ok(src, self.norm1) and _ports_ok(src, self.norm2):
+            return self._forward_ports(src, pos, reference_points, spatial_shapes, level_start_index, padding_mask, carry)
+        if carry is not None:
+            carry["q"] = None
         vd = self.self_attn.active_value_dtype(src)          # 16-bit value path (opt-in): no up-cast of src for it; the query path stays fp32
         with torch.autocast(device_type=src.device.type, enabled=False):
             q = src.float() if pos is None else src.float() + pos.float()
@@ -95,6 +137,27 @@ class DeformableTransformerEncoderLayer(nn.Module):
         src = _drop_add_norm(attn, src, self.dropout1, self.norm1)
         ffn = self.linear2(_ffn_hidden(src, self.linear1, self.activation, self.dropout2))
         return _drop_add_norm(ffn, src, self.dropout3, self.norm2)
+
+    def _forward_ports(self, src, pos, reference_points, spatial_shapes, level_start_index, padding_mask, carry):
+        """The same layer through the extra ports of the norm kernels: output_proj + norm1 and linear2 + norm2 are one autograd node
+        each, norm1 also stores its output in the autocast dtype for linear1, norm2 also stores `output + pos` for the next layer."""
+        vd = self.self_attn.active_value_dtype(src)
+        lp = _ffn_lp_dtype(src, self.linear1, self.activation)
+        q = carry.get("q") if carry is not None else None
+        with torch.autocast(device_type=src.device.type, enabled=False):
+            if q is None:
+                q = src if pos is None else src + pos.float()
+            attn = self.self_attn(q, reference_points, src, spatial_shapes, level_start_index, padding_mask,
+                                  value_dtype=vd, project_output=False)[0]
+            src, _, src_lp = _linear_drop_add_norm_ports(*self.self_attn.output_proj_operands(attn, vd), src, self.dropout1, self.norm1, None, lp)
+        h = _ffn_hidden(src, self.linear1, self.activation, self.dropout2, src_lp)
+        want = (carry is not None and carry.get("want") and pos is not None and pos.dtype == torch.float32 and pos.shape == src.shape)
+        l2 = self.linear2
+        out, q_next, _ = _linear_drop_add_norm_ports(h, amp_cache.lookup(l2.weight), None if l2.bias is None else amp_cache.lookup(l2.bias), src,
+                                                     self.dropout3, self.norm2, pos if want else None, None)
+        if carry is not None:
+            carry["q"] = q_next
+        return out
 
 
 class DeformableTransformerEncoder(nn.Module):
@@ -123,8 +186,14 @@ class DeformableTransformerEncoder(nn.Module):
         ref = memo("enc_ref_points", getattr(valid_ratios, "_ocpg_key", None), src.device,
                    lambda: self.get_reference_points(spatial_shapes, valid_ratios, src.device))
         out = src
-        for layer in self.layers:
-            out = layer(out, pos, ref, spatial_shapes, level_start_index, padding_mask)
+        if not fused_ln_func.PORTS:
+            for layer in self.layers:
+                out = layer(out, pos, ref, spatial_shapes, level_start_index, padding_mask)
+            return out
+        carry = {"q": None}
+        for i, layer in enumerate(self.layers):
+            carry["want"] = i + 1 < len(self.layers)         # the last layer's output feeds the decoder: no query to prepare
+            out = layer(out, pos, ref, spatial_shapes, level_start_index, padding_mask, carry=carry)
         return out
 
 
@@ -146,7 +215,14 @@ class DeformableTransformerDecoderLayer(nn.Module):
         self.dropout4 = nn.Dropout(dropout)
         self.norm3 = nn.LayerNorm(d_model)
 
-    def forward(self, tgt, query_pos, reference_points, src, src_spatial_shapes, level_start_index, src_padding_mask=None):
+    def forward(self, tgt, query_pos, reference_points, src, src_spatial_shapes, level_start_index, src_padding_mask=None, carry=None):
+        """carry (a dict the decoder hands to its layers in turn, or None): carry["qp"] = query_pos as a dense tensor, carry["q"] =
+        this layer's `tgt + query_pos`, formed by the previous layer's norm3 kernel; with carry["want"] this layer leaves the next one's."""
+        if (query_pos is not None and query_pos.dtype == torch.float32 and query_pos.shape == tgt.shape
+                and all(_ports_ok(tgt, n) for n in (self.norm1, self.norm2, self.norm3))):
+            return self._forward_ports(tgt, query_pos, reference_points, src, src_spatial_shapes, level_start_index, src_padding_mask, carry)
+        if carry is not None:
+            carry["q"] = None
         qk = tgt if query_pos is None else tgt + query_pos
         sa = self.self_attn(qk.transpose(0, 1), qk.transpose(0, 1), tgt.transpose(0, 1)).transpose(0, 1)
         tgt = _drop_add_norm(sa, tgt, self.dropout2, self.norm2)
@@ -158,6 +234,30 @@ class DeformableTransformerDecoderLayer(nn.Module):
         tgt = _drop_add_norm(ca, tgt, self.dropout1, self.norm1)
         ffn = self.linear2(_ffn_hidden(tgt, self.linear1, self.activation, self.dropout3))
         return _drop_add_norm(ffn, tgt, self.dropout4, self.norm3), loc, weights
+
+    def _forward_ports(self, tgt, query_pos, reference_points, src, src_spatial_shapes, level_start_index, src_padding_mask, carry):
+        """The same layer through the extra ports of the norm kernels: ONE `y + query_pos` per LayerNorm output, stored by the kernel
+        that stores y (norm2: the cross-attention's query; norm3: the next layer's self-attention q / k), and norm1's output once more
+        in the autocast dtype for linear1."""
+        qp = carry.get("qp") if carry is not None else None
+        if qp is None:
+            qp = query_pos
+        qk = carry.get("q") if carry is not None else None
+        if qk is None:
+            qk = tgt + query_pos
+        sa = self.self_attn(qk.transpose(0, 1), qk.transpose(0, 1), tgt.transpose(0, 1)).transpose(0, 1)
+        tgt, q, _ = _drop_add_norm_ports(sa, tgt, self.dropout2, self.norm2, qp, None)
+        vd = self.cross_attn.active_value_dtype(src)
+        with torch.autocast(device_type=tgt.device.type, enabled=False):
+            ca, loc, weights = self.cross_attn(q, reference_points, src.float() if vd is None else src, src_spatial_shapes, level_start_index,
+                                               src_padding_mask, value_dtype=vd)
+        tgt, _, tgt_lp = _drop_add_norm_ports(ca, tgt, self.dropout1, self.norm1, None, _ffn_lp_dtype(tgt, self.linear1, self.activation))
+        ffn = self.linear2(_ffn_hidden(tgt, self.linear1, self.activation, self.dropout3, tgt_lp))
+        want = carry is not None and carry.get("want")
+        out, q_next, _ = _drop_add_norm_ports(ffn, tgt, self.dropout4, self.norm3, qp if want else None, None)
+        if carry is not None:
+            carry["q"] = q_next
+        return out, loc, weights
 
 
 class DeformableTransformerDecoder(nn.Module):
@@ -181,13 +281,21 @@ class DeformableTransformerDecoder(nn.Module):
         inter, inter_refs, inter_samples = [], [], []
         self.box_deltas = [] if self.bbox_embed is not None else None      # handed to the caller's box head (same module, same input)
         samples_keep = None
+        carry = None
+        if fused_ln_func.PORTS and query_pos is not None and out.is_cuda:
+            # query_pos arrives as an expanded view: the kernels read a dense addend, made once for all layers
+            carry = {"q": None, "qp": query_pos.contiguous()}
         for lid, layer in enumerate(self.layers):
             if reference_points.shape[-1] == 4:
                 ref_in = reference_points[:, :, None] * torch.cat([src_valid_ratios, src_valid_ratios], -1)[:, None]
             else:
                 assert reference_points.shape[-1] == 2
                 ref_in = reference_points[:, :, None] * src_valid_ratios[:, None]
-            out, loc, weights = layer(out, query_pos, ref_in, src, src_spatial_shapes, src_level_start_index, src_padding_mask)
+            if carry is None:
+                out, loc, weights = layer(out, query_pos, ref_in, src, src_spatial_shapes, src_level_start_index, src_padding_mask)
+            else:
+                carry["want"] = lid + 1 < len(self.layers)
+                out, loc, weights = layer(out, query_pos, ref_in, src, src_spatial_shapes, src_level_start_index, src_padding_mask, carry=carry)
 
             if self.compute_samples:
                 n, lq = loc.shape[:2]

@@ -11,6 +11,8 @@ the kernel adds to its offset; the captured step ends with `advance()` (base += 
 replay r of a graph captured at host counter c0 uses offsets c0 + r * J + j -- exactly the offsets eager step r would have used
 (tests/test_graph_gpu.py: consecutive replays differ, replay k == eager step k).
 """
+import os
+
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -19,6 +21,9 @@ from ...._lib import check, lib
 from .gemm_func import mm
 
 _DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+# A/B switch, read once: the extra ports of the dropout+add+LayerNorm kernels (y + addend and a 16-bit copy of y forward, up to three
+# gradient addends and the Linear's bias-gradient partials backward) and the Linear + dropout/add/LN autograd node; 0 = the plain calls
+PORTS = os.environ.get("OCPG_FUSED_LN_PORTS", "1") != "0"
 _calls = [0]
 _active = [None]            # the GraphRng whose capture is in progress (at most one per process)
 
@@ -114,6 +119,120 @@ class DropoutAddLayerNorm(Function):
         return (None if gx is None else gx.view(xshape), None if gres is None else gres.view(rshape), dgb[0], dgb[1], None, None, None)
 
 
+def _dal_fwd_ex(x2, res2, gamma, beta, p, eps, seed, offset, base, addend, lp_dtype):
+    """-> (y, stats, y_add | None, y_lp | None): the forward kernel with its extra ports"""
+    r, c = x2.shape
+    y = torch.empty((r, c), dtype=torch.float32, device=x2.device)
+    stats = torch.empty((2, r), dtype=torch.float32, device=x2.device)
+    y_add = torch.empty_like(y) if addend is not None else None
+    y_lp = torch.empty((r, c), dtype=lp_dtype, device=x2.device) if lp_dtype is not None else None
+    check(lib().ocpg_dropout_add_ln_fwd_ex(x2.data_ptr(), res2.data_ptr(), gamma.data_ptr(), beta.data_ptr(), r, c, float(eps), float(p), seed,
+                                           offset, base, _DT[x2.dtype], y.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(),
+                                           None if addend is None else addend.data_ptr(), None if y_add is None else y_add.data_ptr(),
+                                           None if y_lp is None else y_lp.data_ptr(), 0 if lp_dtype is None else _DT[lp_dtype], _st()),
+          "ocpg_dropout_add_ln_fwd_ex")
+    return y, stats, y_add, y_lp
+
+
+def _dal_bwd_ex(grads, x2, res2, gamma, stats, p, seed, offset, base, want_gx, want_gres, want_gxsum):
+    """grads: the gradients of (y, y_add, y_lp) that arrived (1..3 tensors [R, C], fp32 / bf16 / fp16), summed inside the kernel
+    -> (gx | None, gres | None, dgb_part, gxsum_part | None)"""
+    r, c = x2.shape
+    gs = []
+    for g in grads:
+        g = g.reshape(r, c)
+        if g.dtype not in _DT:
+            g = g.float()
+        gs.append(g if g.is_contiguous() else g.contiguous())
+    gs += [None] * (3 - len(gs))
+    gx = torch.empty_like(x2) if want_gx else None
+    gres = torch.empty_like(res2) if want_gres else None
+    slots = lib().ocpg_dropout_add_ln_bwd_slots(r)
+    part = torch.empty((slots, 2, c), dtype=torch.float32, device=x2.device)
+    gxsum = torch.empty((slots, c), dtype=torch.float32, device=x2.device) if want_gxsum else None
+    ga = []
+    for g in gs:
+        ga += [None, 0] if g is None else [g.data_ptr(), _DT[g.dtype]]
+    check(lib().ocpg_dropout_add_ln_bwd_ex(*ga, x2.data_ptr(), res2.data_ptr(), gamma.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(),
+                                           r, c, p, seed, offset, base, _DT[x2.dtype], None if gx is None else gx.data_ptr(),
+                                           None if gres is None else gres.data_ptr(), part.data_ptr(),
+                                           None if gxsum is None else gxsum.data_ptr(), _st()),
+          "ocpg_dropout_add_ln_bwd_ex")
+    return gx, gres, part, gxsum
+
+
+class DropoutAddLayerNormPorts(Function):
+    """DropoutAddLayerNorm with the kernels' extra ports: -> (y, y + addend | None, y in lp_dtype | None).  The backward hands the
+    gradients that arrived for the three outputs to the kernel as they are (no cast, no add); an output nobody used is skipped."""
+
+    @staticmethod
+    def forward(ctx, x, res, gamma, beta, p, eps, rng, addend, lp_dtype):
+        c = x.shape[-1]
+        x2, res2 = x.reshape(-1, c).contiguous(), res.reshape(-1, c).contiguous()
+        ad2 = None if addend is None else addend.reshape(-1, c).contiguous()
+        seed, offset, base = _unpack(rng)
+        y, stats, y_add, y_lp = _dal_fwd_ex(x2, res2, gamma, beta, p, eps, seed, offset, base, ad2, lp_dtype)
+        ctx.save_for_backward(x2, res2, gamma, stats)
+        ctx.meta = (float(p), seed, offset, base, x.shape, res.shape, None if addend is None else addend.shape)
+        ctx.set_materialize_grads(False)
+        return y.view(res.shape), None if y_add is None else y_add.view(res.shape), None if y_lp is None else y_lp.view(res.shape)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy, gadd, glp):
+        x2, res2, gamma, stats = ctx.saved_tensors
+        p, seed, offset, base, xshape, rshape, ashape = ctx.meta
+        grads = [g for g in (gy, gadd, glp) if g is not None]
+        if not grads:
+            return (None,) * 9
+        gx, gres, part, _ = _dal_bwd_ex(grads, x2, res2, gamma, stats, p, seed, offset, base, ctx.needs_input_grad[0], ctx.needs_input_grad[1], False)
+        dgb = part.sum(0)
+        ga = gadd.reshape(ashape) if (gadd is not None and ctx.needs_input_grad[7]) else None
+        return (None if gx is None else gx.view(xshape), None if gres is None else gres.view(rshape), dgb[0], dgb[1], None, None, None, ga, None)
+
+
+class LinearDropoutAddLayerNorm(Function):
+    """LayerNorm(res + dropout(x2 W^T + b)) as ONE autograd node, for a Linear over many rows (amp_cache.TokenLinearFunction's GEMMs):
+    forward = GEMM with its bias epilogue + the dropout/add/LN kernel; backward = that kernel's backward, which also leaves the partial
+    column sums of the Linear's output gradient (its bias gradient), then the input-gradient GEMM and the row-split weight gradient."""
+
+    @staticmethod
+    def forward(ctx, x2, w, b, res, gamma, beta, p, eps, rng, addend, lp_dtype):
+        from ...amp_cache import deferrable
+        h = mm(x2, w, True, b)
+        c = h.shape[-1]
+        res2 = res.reshape(-1, c).contiguous()
+        ad2 = None if addend is None else addend.reshape(-1, c).contiguous()
+        seed, offset, base = _unpack(rng)
+        y, stats, y_add, y_lp = _dal_fwd_ex(h, res2, gamma, beta, p, eps, seed, offset, base, ad2, lp_dtype)
+        ctx.save_for_backward(x2, w, h, res2, gamma, stats)
+        ctx.meta = (float(p), seed, offset, base, res.shape, None if addend is None else addend.shape)
+        ctx.has_bias = b is not None
+        ctx.defer_w, ctx.defer_b = deferrable(w), b is not None and deferrable(b) and b.dtype == h.dtype
+        ctx.set_materialize_grads(False)
+        return y.view(res.shape), None if y_add is None else y_add.view(res.shape), None if y_lp is None else y_lp.view(res.shape)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy, gadd, glp):
+        from ...amp_cache import defer_sum, weight_grad
+        x2, w, h, res2, gamma, stats = ctx.saved_tensors
+        p, seed, offset, base, rshape, ashape = ctx.meta
+        grads = [g for g in (gy, gadd, glp) if g is not None]
+        if not grads:
+            return (None,) * 11
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        gh, gres, part, gxsum = _dal_bwd_ex(grads, h, res2, gamma, stats, p, seed, offset, base, True, ctx.needs_input_grad[3], need_b)
+        dgb = part.sum(0)
+        gb = None
+        if need_b:
+            gb = defer_sum(gxsum, h.dtype) if (ctx.defer_b and h.dtype != torch.float32) else gxsum.sum(0).to(h.dtype)
+        gx = mm(gh, w) if ctx.needs_input_grad[0] else None
+        gw = weight_grad(gh, x2, ctx.defer_w) if ctx.needs_input_grad[1] else None
+        ga = gadd.reshape(ashape) if (gadd is not None and ctx.needs_input_grad[9]) else None
+        return (gx, gw, gb, None if gres is None else gres.view(rshape), dgb[0], dgb[1], None, None, None, ga, None)
+
+
 class LinearBiasReluDropout(Function):
     @staticmethod
     def forward(ctx, x2, w, b, p, rng, splits):
@@ -151,6 +270,16 @@ class LinearBiasReluDropout(Function):
 
 def supported(x, res, c):
     return (x.is_cuda and x.dtype in _DT and res.dtype == torch.float32 and c % 4 == 0 and c <= 2048 and x.shape == res.shape)
+
+
+def dropout_add_layer_norm_ports(x, res, norm, p, addend=None, lp_dtype=None, rng=None):
+    """-> (norm(res + dropout_p(x)) fp32, that + addend (fp32, or None), that in lp_dtype (bf16 / fp16, or None)): one pass each way."""
+    return DropoutAddLayerNormPorts.apply(x, res, norm.weight, norm.bias, p, norm.eps, rng, addend, lp_dtype)
+
+
+def linear_dropout_add_layer_norm(x2, w, b, res, norm, p, addend=None, lp_dtype=None, rng=None):
+    """The same three outputs for x = x2 W^T + b (x2 [R, K], w, b of one dtype): Linear + dropout/add/LN as one autograd node."""
+    return LinearDropoutAddLayerNorm.apply(x2, w, b, res, norm.weight, norm.bias, p, norm.eps, rng, addend, lp_dtype)
 
 
 def dropout_add_layer_norm(x, res, norm, p, rng=None):

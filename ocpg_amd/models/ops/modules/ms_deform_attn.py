@@ -151,9 +151,10 @@ class MSDeformAttn(nn.Module):
         nn.init.zeros_(self.output_proj.bias)
 
     def forward(self, query, reference_points, input_flatten, input_spatial_shapes, input_level_start_index,
-                input_padding_mask=None, value_dtype=_UNSET):
+                input_padding_mask=None, value_dtype=_UNSET, project_output=True):
         """value_dtype: what a caller that wraps the module in autocast(enabled=False) got from active_value_dtype() (None = fp32);
-        left out, the module asks itself."""
+        left out, the module asks itself.  project_output=False: the first return value is the op's output BEFORE output_proj (the
+        caller applies `output_proj_operands` itself, fused with what follows the module)."""
         N, Lq, _ = query.shape
         vd = self.active_value_dtype(input_flatten) if value_dtype is _UNSET else value_dtype
         _, S, _ = input_flatten.shape
@@ -194,7 +195,7 @@ class MSDeformAttn(nn.Module):
                 # lines 96-110 of the reference module inside the kernels: no softmax / add / split-cat passes over the [N, Lq, 384] projection
                 out, loc, weights = MSDeformAttnFusedFunction.apply(value.contiguous(), input_spatial_shapes, input_level_start_index, both,
                                                                     reference_points, L, P, self._sel_state if SELECT_PATH else None)
-                return (self.output_proj(out) if vd is None else self._linear16(out, self.output_proj, vd)), loc, weights
+                return self._project(out, vd, project_output), loc, weights
             off2, logit2 = torch.split(both, [n_off, M * L * P], dim=-1)      # split: its backward is ONE cat (two slices: 2 x (zeros + copy) + add)
             offsets = off2.view(N, Lq, M, L, P, 2)
             weights = F.softmax(logit2.view(N, Lq, M, L * P), -1).view(N, Lq, M, L, P)
@@ -220,10 +221,22 @@ class MSDeformAttn(nn.Module):
             if fn is not None and fn.supported(input_flatten, vp.weight, vp.bias, loc_c, weights):
                 out = fn.apply(input_flatten, vp.weight, vp.bias, input_padding_mask, input_spatial_shapes, input_level_start_index, loc_c,
                                weights.contiguous())
-                return self.output_proj(out), loc, weights
+                return self._project(out, None, project_output), loc, weights
             value = make_value()          # a shape or dtype the kernels do not serve: today's path
         if SELECT_PATH and Lq == S and loc_c.is_cuda:
             loc_c._ocpg_sel = self._sel_state
         out = MSDeformAttnFunction.apply(value.contiguous(), input_spatial_shapes, input_level_start_index,
                                          loc_c, weights.contiguous(), self.im2col_step)
-        return (self.output_proj(out) if vd is None else self._linear16(out, self.output_proj, vd)), loc, weights
+        return self._project(out, vd, project_output), loc, weights
+
+    def _project(self, out, vd, project_output):
+        if not project_output:
+            return out
+        return self.output_proj(out) if vd is None else self._linear16(out, self.output_proj, vd)
+
+    def output_proj_operands(self, out, vd):
+        """(out, weight, bias) of output_proj as the module itself would hand them to amp_cache.linear for this value dtype."""
+        lin = self.output_proj
+        if vd is None:
+            return out, lin.weight, lin.bias
+        return out.to(vd), amp_cache.lookup(lin.weight).to(vd), amp_cache.lookup(lin.bias).to(vd)
