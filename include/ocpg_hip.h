@@ -21,7 +21,7 @@
  *     grad_value is ACCUMULATED into (scatter-add): the caller zeroes it first, exactly as
  *     ms_deform_attn_cuda.cu:121 does with at::zeros_like; grad_loc / grad_attn are fully overwritten;
  *   - re-entrant and thread-safe; no global state except the GEMM plan cache above (and, in diagnostic builds only, the
- *     EXP_STAMPS counters of the output-tiled MSDeformAttn kernels and of the halo-staged 3x3 convolution).
+ *     EXP_STAMPS counters of the halo-staged 3x3 convolution).
  *
  * Tensor contract of MSDeformAttn (ms_deform_attn_cuda.cu:28-48):
  *   value        [N, S, M, D]          S = sum_l H_l*W_l
@@ -59,7 +59,9 @@ int ocpg_msda_fwd_f64(const double* value, const int64_t* shapes, const int64_t*
 
 /* replaces ms_deform_attn_backward (ms_deform_attn.h:41-61 -> ms_deform_attn_cuda.cu:83-152), float32.
  * shapes_host: as for the forward (may be NULL): selects the column-tile backward (gather kernel for grad_loc /
- * grad_attn + bin-and-sum scatter kernel for grad_value) when Lq == S. */
+ * grad_attn + bin-and-sum scatter kernel for grad_value) when Lq == S and the column scatter serves the shape (D = 16 or 32, a
+ * P and level count its geometry takes, OCPG_MSDA_COL not 0).  Every other call -- NULL, Lq != S, D = 64, ... -- runs the row
+ * kernel that gathers and scatters with fp32 atomics in one launch (D = 4 * 2^k <= 256), or the generic kernel (any D). */
 int ocpg_msda_bwd_f32(const float* value, const int64_t* shapes, const int64_t* level_start,
                       const float* loc, const float* attn, const float* grad_out,
                       int N, int S, int M, int D, int L, int Lq, int P,

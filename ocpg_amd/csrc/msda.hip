@@ -21,8 +21,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-
 #include <cstdlib>
 
 #include "../../include/ocpg_hip.h"
@@ -66,16 +64,11 @@ __global__ __launch_bounds__(256) void msda_fwd_fast(const float* __restrict__ v
   const int NS = L * P;
   const int MD = M * D;
   const int r = tid / G, j = tid % G;
-#ifndef MSDA_ROW_MAJOR
   // XCD-aware mapping: blocks are dealt round-robin over the 8 XCDs, so block % M picks the HEAD; with M == 8 every
   // XCD then gathers only its own head's 128-B slices of `value` (1/8 of the map) through its private 4-MiB L2.
   const long long qrow = (long long)(blockIdx.x / M) * ROWS + r;          // flat (b, q)
   const long long row = qrow * M + (blockIdx.x % M);
   const bool live = qrow * M < rows;
-#else
-  const long long row = (long long)blockIdx.x * ROWS + r;
-  const bool live = row < rows;
-#endif
   if (live) {
     const float* lrow = loc + row * NS * 2;
     const float* arow = attn + row * NS;
@@ -234,7 +227,7 @@ __global__ __launch_bounds__(256) void msda_fwd_generic(const T* __restrict__ va
 
 // ------------------------------------------------------------------------------------------------------
 // Gather side of the backward (grad_loc, grad_attn; cuh:87-159 without the col2im scatter): row kernel, used with the
-// column-tile scatter kernel (msda_col.hip).  Differences from msda_bwd_fast<G, false>:
+// column-tile scatter kernel (msda_col.hip).  Differences from the gather in msda_bwd_fast<G>:
 //   * validity is folded into the per-axis weights (hy' = y0 >= 0 ? 1-ly : 0 ...) and the corner addresses are clamped
 //     into the map, so the inner loop has no masks and no selects: 4 unconditional 16-B loads, packed FMAs;
 //   * 4 samples are reduced together by a DPP reduce-scatter (12 moves) instead of 9 LDS-crossbar shuffles per sample.
@@ -367,7 +360,7 @@ __global__ __launch_bounds__(256) void msda_bwd_gather_row(const float* __restri
 
 // ------------------------------------------------------------------------------------------------------
 // Fast backward (plain float-atomic scatter for grad_value).
-template <int G, bool SCATTER = true>
+template <int G>
 __global__ __launch_bounds__(256) void msda_bwd_fast(const float* __restrict__ value, const int64_t* __restrict__ shapes,
                                                      const int64_t* __restrict__ level_start, const float* __restrict__ loc,
                                                      const float* __restrict__ attn, const float* __restrict__ gout, int S, int M,
@@ -388,16 +381,9 @@ __global__ __launch_bounds__(256) void msda_bwd_fast(const float* __restrict__ v
   const int NS = L * P;
   const int MD = M * D;
   const int r = tid / G, j = tid % G;
-#ifndef MSDA_ROW_MAJOR
-  // XCD-aware mapping: blocks are dealt round-robin over the 8 XCDs, so block % M picks the HEAD; with M == 8 every
-  // XCD then gathers only its own head's 128-B slices of `value` (1/8 of the map) through its private 4-MiB L2.
-  const long long qrow = (long long)(blockIdx.x / M) * ROWS + r;          // flat (b, q)
+  const long long qrow = (long long)(blockIdx.x / M) * ROWS + r;          // head fastest: one head per XCD L2 (see msda_fwd_fast)
   const long long row = qrow * M + (blockIdx.x % M);
   const bool live = qrow * M < rows;
-#else
-  const long long row = (long long)blockIdx.x * ROWS + r;
-  const bool live = row < rows;
-#endif
   if (live) {
     const float* lrow = loc + row * NS * 2;
     const float* arow = attn + row * NS;
@@ -434,11 +420,9 @@ __global__ __launch_bounds__(256) void msda_bwd_fast(const float* __restrict__ v
       for (int k = 0; k < 4; ++k) {
         if (rec.mask & (1 << k)) {
           const float4 v = ld4(vbase + rec.off00 + offs[k]);
-          if constexpr (SCATTER) {
-            float* g = gsc + rec.off00 + offs[k];        // lane j owns channels {j, j+G, j+2G, j+3G}: contiguous 4G-byte segments
+          float* g = gsc + rec.off00 + offs[k];        // lane j owns channels {j, j+G, j+2G, j+3G}: contiguous 4G-byte segments
 #pragma unroll
-            for (int c = 0; c < 4; ++c) atomicAdd(g + c * G, w[k] * gs[c] * rec.a);
-          }
+          for (int c = 0; c < 4; ++c) atomicAdd(g + c * G, w[k] * gs[c] * rec.a);
           val.x += w[k] * v.x; val.y += w[k] * v.y; val.z += w[k] * v.z; val.w += w[k] * v.w;
           dxs.x += dxc[k] * v.x; dxs.y += dxc[k] * v.y; dxs.z += dxc[k] * v.z; dxs.w += dxc[k] * v.w;
           dys.x += dyc[k] * v.x; dys.y += dyc[k] * v.y; dys.z += dyc[k] * v.z; dys.w += dyc[k] * v.w;
@@ -454,311 +438,6 @@ __global__ __launch_bounds__(256) void msda_bwd_fast(const float* __restrict__ v
     if (j == 0) {
       gattn[row * NS + s] = ga;
       *reinterpret_cast<float2*>(gloc + (row * NS + s) * 2) = make_float2(gx, gy);
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// Tiled backward for self-attention over the value's own pixels (Lq == S, the encoder): LDS-privatised grad_value.
-//
-// Float atomics execute at the memory side at ~1.3 TB/s chip-wide (MI355X_MICROARCH.md, "Global float atomics"); the
-// plain scatter above issues 4*L*P*D*4 = 8 KiB of atomic bytes per (query, head) -- 1.67 GB per encoder layer at
-// config #2 -- and is bound by exactly that.  Here one workgroup owns a TILE x TILE patch of query pixels of one
-// level for ONE head.  Neighbouring queries sample neighbouring pixels, so for every destination level the
-// patch's samples fall into a small window whose origin is found from the data (min corner over the patch) and
-// whose size the host derives from the patch extent plus a margin.  Contributions inside the window are summed in
-// LDS (ds_add_f32); the window is flushed once with global atomics (one 128-B segment per pixel and head); anything
-// outside the window falls back to a direct global atomic, so the result never depends on the locality
-// assumption -- only the speed does.
-// The LDS accumulators are DOUBLES: measured on gfx950 (tools/ubench/lds_atomic.hip) a ds_add_f32 wave-instruction
-// costs ~193 cycles per CU (lane-serial), ds_add_f64 ~9, ds_add_u32 ~5 -- f64 is 20x faster than f32 and also makes
-// the in-window sum more accurate than the reference's fp32 atomics; it is rounded to fp32 once at the flush.
-constexpr int kTile = 8;
-constexpr int kMaxTileLevels = 8;
-
-struct TileGeom {
-  int L;
-  int ntiles;                               // tiles per (b, m)
-  int tile_base[kMaxTileLevels + 1];        // first tile id of each query level
-  int tiles_x[kMaxTileLevels];              // tiles per row of each query level
-  int win_w[kMaxTileLevels][kMaxTileLevels];    // [query level][dest level] window width  (pixels)
-  int win_h[kMaxTileLevels][kMaxTileLevels];
-  int win_off[kMaxTileLevels][kMaxTileLevels];  // window start in the LDS accumulator (pixels)
-  int win_pixels[kMaxTileLevels];           // total window pixels of a query level
-};
-
-struct __attribute__((aligned(16))) TileRec {
-  int off00;     // element offset of corner (y0,x0) relative to value[b,0,m,0] (may be virtual)
-  int lvl_mask;  // level << 4 | corner mask
-  float a, ly, lx;
-  int x0, y0;
-  int pad;
-};
-
-#ifndef MSDA_WPE
-#define MSDA_WPE 3      // waves per SIMD the register allocator is held to (152 VGPRs unconstrained = 3)
-#endif
-template <int G, int NB, bool GATHER = true>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSDA_WPE, 8))) void msda_bwd_tiled(const float* __restrict__ value, const int64_t* __restrict__ shapes,
-                                                      const int64_t* __restrict__ level_start, const float* __restrict__ loc,
-                                                      const float* __restrict__ attn, const float* __restrict__ gout, int S, int M,
-                                                      int P, TileGeom geo, float* __restrict__ gvalue, float* __restrict__ gloc,
-                                                      float* __restrict__ gattn) {
-  constexpr int D = 4 * G;
-  constexpr int ROWS = 256 / G;                      // queries processed per pass
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ int lvlH[kMaxTileLevels], lvlW[kMaxTileLevels], lvlS[kMaxTileLevels];
-  __shared__ int win_ox[kMaxTileLevels], win_oy[kMaxTileLevels];
-  const int L = geo.L;
-  const int NS = L * P;
-  TileRec* recs = reinterpret_cast<TileRec*>(smem);                                  // [ROWS][P]  (one level at a time)
-  double* acc = reinterpret_cast<double*>(smem + (size_t)ROWS * P * sizeof(TileRec));  // [window pixels][D], fp64: see below
-  const int tid = threadIdx.x;
-  if (tid < L) {
-    lvlH[tid] = (int)shapes[2 * tid];
-    lvlW[tid] = (int)shapes[2 * tid + 1];
-    lvlS[tid] = (int)level_start[tid];
-    win_ox[tid] = 0x7fffffff;
-    win_oy[tid] = 0x7fffffff;
-  }
-  // decode (b, m, tile): all uniform
-  int bid = blockIdx.x;
-#ifndef MSDA_ROW_MAJOR
-  const int m = bid % M;          // head fastest: block % 8 == XCD (round-robin dispatch) -> one head per XCD L2
-  bid /= M;
-  const int tile = bid % geo.ntiles;
-  const int b = bid / geo.ntiles;
-#else
-  const int tile = bid % geo.ntiles;
-  bid /= geo.ntiles;
-  const int m = bid % M;
-  const int b = bid / M;
-#endif
-  int lq = 0;
-  while (lq + 1 < L && tile >= geo.tile_base[lq + 1]) ++lq;
-  const int t_in = tile - geo.tile_base[lq];
-  const int ty0 = (t_in / geo.tiles_x[lq]) * kTile, tx0 = (t_in % geo.tiles_x[lq]) * kTile;
-  __syncthreads();
-  const int Hq = lvlH[lq], Wq = lvlW[lq], Sq = lvlS[lq];
-  const int th = min(kTile, Hq - ty0), tw = min(kTile, Wq - tx0);
-  const int nq = th * tw;                                                 // queries in this tile (<= 64)
-  const int MD = M * D;
-
-  // pass A: window origins = min (y0, x0) over the tile's valid samples, per destination level.  With 256 % NS == 0 a lane
-  // sees the same sample slot (hence level) in every iteration: running minimum in registers, one LDS atomic pair per lane
-  {
-    const bool fixed = (256 % NS) == 0;
-    int my = 0x7fffffff, mx = 0x7fffffff;
-    for (int i = tid; i < nq * NS; i += 256) {
-      const int qi = i / NS, s = i % NS, l = s / P;
-      const int q = Sq + (ty0 + qi / tw) * Wq + tx0 + qi % tw;
-      const long long row = ((long long)b * S + q) * M + m;
-      const float2 xy = *reinterpret_cast<const float2*>(loc + (row * NS + s) * 2);
-      const int H = lvlH[l], W = lvlW[l];
-      const float h_im = xy.y * (float)H - 0.5f, w_im = xy.x * (float)W - 0.5f;
-      if (h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W) {
-        const int y0 = max((int)floorf(h_im), 0), x0 = max((int)floorf(w_im), 0);
-        if (fixed) { my = min(my, y0); mx = min(mx, x0); }
-        else { atomicMin(&win_oy[l], y0); atomicMin(&win_ox[l], x0); }
-      }
-    }
-    if (fixed && my != 0x7fffffff) {
-      const int l = (tid % NS) / P;
-      atomicMin(&win_oy[l], my);
-      atomicMin(&win_ox[l], mx);
-    }
-  }
-  __syncthreads();
-
-  const int r = tid / G, j = tid % G;
-  const long long boff = (long long)b * S * MD + m * D + 4 * j;
-  // the output gradient of this lane's query in every pass: loaded ONCE (it does not depend on the level)
-  constexpr int PASSES = (kTile * kTile + ROWS - 1) / ROWS;
-  float4 go_p[PASSES];
-  float gs_p[PASSES][4];
-#pragma unroll
-  for (int ps = 0; ps < PASSES; ++ps) {
-    const int qi = ps * ROWS + r;
-    go_p[ps] = make_float4(0.f, 0.f, 0.f, 0.f);
-    gs_p[ps][0] = gs_p[ps][1] = gs_p[ps][2] = gs_p[ps][3] = 0.f;
-    if (qi < nq) {
-      const int q = Sq + (ty0 + qi / tw) * Wq + tx0 + qi % tw;
-      const long long row = ((long long)b * S + q) * M + m;
-      if constexpr (GATHER) go_p[ps] = ld4(gout + row * D + 4 * j);
-      gs_p[ps][0] = gout[row * D + j]; gs_p[ps][1] = gout[row * D + j + G]; gs_p[ps][2] = gout[row * D + j + 2 * G]; gs_p[ps][3] = gout[row * D + j + 3 * G];
-    }
-  }
-  // (level, pass) steps; the raw (location, weight) of the NEXT step's records are requested before this step's main loop and
-  // consumed after it, so their latency hides behind the scatter/gather work instead of standing alone between two barriers
-  const int npass = (nq + ROWS - 1) / ROWS;
-  const int nsteps = L * npass;
-  const bool pf_ok = ROWS * P <= 256;        // one record per lane per step
-  float2 pxy = make_float2(0.f, 0.f);
-  float pa = 0.f;
-  auto fetch = [&](int st) {
-    const int l_ = st / npass, q0_ = (st % npass) * ROWS;
-    const int nrow_ = min(ROWS, nq - q0_);
-    if (tid < nrow_ * P) {
-      const int qi = q0_ + tid / P;
-      const int q = Sq + (ty0 + qi / tw) * Wq + tx0 + qi % tw;
-      const long long row = ((long long)b * S + q) * M + m;
-      const int s = l_ * P + tid % P;
-      pxy = *reinterpret_cast<const float2*>(loc + (row * NS + s) * 2);
-      pa = attn[row * NS + s];
-    }
-  };
-  if (pf_ok && nsteps > 0) fetch(0);
-  int H = 0, W = 0, ww = 0, wh = 0, ox = 0, oy = 0, rowstride = 0;
-  const float* vbase = value;
-  float* gvalue_l = gvalue;
-  for (int st = 0; st < nsteps; ++st) {              // one destination level at a time: one LDS window live
-    const int l = st / npass, pass = st % npass, q0 = pass * ROWS;
-    if (pass == 0) {
-      H = lvlH[l]; W = lvlW[l];
-      ww = geo.win_w[lq][l]; wh = geo.win_h[lq][l];
-      ox = (win_ox[l] == 0x7fffffff) ? 0 : max(0, min(win_ox[l], W - ww));   // keep the window inside the map
-      oy = (win_oy[l] == 0x7fffffff) ? 0 : max(0, min(win_oy[l], H - wh));
-      rowstride = W * MD;
-      vbase = value + boff + (long long)lvlS[l] * MD;
-      gvalue_l = gvalue + (long long)b * S * MD + m * D + (long long)lvlS[l] * MD;
-      for (int i = tid; i < ww * wh * D; i += 256) acc[i] = 0.0;
-    }
-    {
-      const int nrow = min(ROWS, nq - q0);
-      for (int i = tid; i < nrow * P; i += 256) {     // records of this step: P samples per query
-        float2 xy;
-        float a_;
-        if (pf_ok) { xy = pxy; a_ = pa; }
-        else {
-          const int qi = q0 + i / P;
-          const int q = Sq + (ty0 + qi / tw) * Wq + tx0 + qi % tw;
-          const long long row = ((long long)b * S + q) * M + m;
-          const int s = l * P + i % P;
-          xy = *reinterpret_cast<const float2*>(loc + (row * NS + s) * 2);
-          a_ = attn[row * NS + s];
-        }
-        const float h_im = xy.y * (float)H - 0.5f, w_im = xy.x * (float)W - 0.5f;
-        TileRec rec;
-        rec.a = a_;
-        rec.pad = 0;
-        if (h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W) {
-          const int y0 = (int)floorf(h_im), x0 = (int)floorf(w_im);
-          rec.ly = h_im - (float)y0;
-          rec.lx = w_im - (float)x0;
-          const bool y0ok = y0 >= 0, y1ok = y0 + 1 <= H - 1, x0ok = x0 >= 0, x1ok = x0 + 1 <= W - 1;
-          rec.lvl_mask = (y0ok && x0ok ? 1 : 0) | (y0ok && x1ok ? 2 : 0) | (y1ok && x0ok ? 4 : 0) | (y1ok && x1ok ? 8 : 0);
-          rec.off00 = (y0 * W + x0) * MD;
-          rec.x0 = x0;
-          rec.y0 = y0;
-        } else {
-          rec.ly = rec.lx = 0.f;
-          rec.lvl_mask = 0;
-          rec.off00 = 0;
-          rec.x0 = rec.y0 = 0;
-        }
-        recs[i] = rec;
-      }
-      if (pf_ok && st + 1 < nsteps) fetch(st + 1);
-      __syncthreads();
-      if (r < nrow) {     // whole G-lane groups take the branch together
-        const int qi = q0 + r;
-        const int q = Sq + (ty0 + qi / tw) * Wq + tx0 + qi % tw;
-        const long long row = ((long long)b * S + q) * M + m;
-        float4 go = go_p[0];
-        float gs[4] = {gs_p[0][0], gs_p[0][1], gs_p[0][2], gs_p[0][3]};
-#pragma unroll
-        for (int ps = 1; ps < PASSES; ++ps)
-          if (pass == ps) { go = go_p[ps]; gs[0] = gs_p[ps][0]; gs[1] = gs_p[ps][1]; gs[2] = gs_p[ps][2]; gs[3] = gs_p[ps][3]; }
-        const TileRec* rr = recs + r * P;
-        const int offs[4] = {0, MD, rowstride, rowstride + MD};
-        for (int p0 = 0; p0 < P; p0 += NB) {
-          TileRec rec[NB];
-          float4 v[NB][4];
-          float red[NB][3];
-#pragma unroll
-          for (int i = 0; i < NB; ++i) rec[i] = rr[p0 + i];
-          if constexpr (GATHER) {
-#pragma unroll
-            for (int i = 0; i < NB; ++i)    // all corner loads of the batch in flight before the first use
-#pragma unroll
-              for (int k = 0; k < 4; ++k) v[i][k] = ld4((rec[i].lvl_mask & (1 << k)) ? vbase + rec[i].off00 + offs[k] : vbase);
-          }
-#pragma unroll
-          for (int i = 0; i < NB; ++i) {
-            const int mask = rec[i].lvl_mask;
-            const float hy = 1.f - rec[i].ly, hx = 1.f - rec[i].lx;
-            const float w[4] = {hy * hx, hy * rec[i].lx, rec[i].ly * hx, rec[i].ly * rec[i].lx};
-            const float dyc[4] = {-hx, -rec[i].lx, hx, rec[i].lx};
-            const float dxc[4] = {-hy, hy, -rec[i].ly, rec[i].ly};
-            const float a = mask ? rec[i].a : 0.f;
-            const float4 tg = make_float4(go.x * a, go.y * a, go.z * a, go.w * a);
-            float4 val = make_float4(0.f, 0.f, 0.f, 0.f);
-            float4 dxs = val, dys = val;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              if (mask & (1 << k)) {
-                const int px = rec[i].x0 + (k & 1) - ox, py = rec[i].y0 + (k >> 1) - oy;
-                // scatter: lane j owns channels {j, j+G, j+2G, j+3G} here, so one atomic instruction covers G
-                // CONSECUTIVE floats per row (contiguous 4G-byte segments in memory, G consecutive LDS banks)
-                if (px >= 0 && px < ww && py >= 0 && py < wh) {      // inside the privatised window: ds_add_f32
-                  const int pp = py * ww + px;
-                  double* gl_ = acc + pp * D + j;                     // bank-group swizzle: channel group i sits in slot (i+pp)&3
-#pragma unroll
-                  for (int c = 0; c < 4; ++c) atomicAdd(gl_ + ((c + pp) & 3) * G, (double)(w[k] * gs[c] * a));   // ds_add_f64
-                } else {                                              // outside: straight to memory
-                  float* g = gvalue_l + rec[i].off00 + offs[k] + j;
-#pragma unroll
-                  for (int c = 0; c < 4; ++c) atomicAdd(g + c * G, w[k] * gs[c] * a);
-                }
-                if constexpr (GATHER) {
-                  const float4 vv = v[i][k];
-                  val.x += w[k] * vv.x; val.y += w[k] * vv.y; val.z += w[k] * vv.z; val.w += w[k] * vv.w;
-                  dxs.x += dxc[k] * vv.x; dxs.y += dxc[k] * vv.y; dxs.z += dxc[k] * vv.z; dxs.w += dxc[k] * vv.w;
-                  dys.x += dyc[k] * vv.x; dys.y += dyc[k] * vv.y; dys.z += dyc[k] * vv.z; dys.w += dyc[k] * vv.w;
-                }
-              }
-            }
-            red[i][0] = mask ? go.x * val.x + go.y * val.y + go.z * val.z + go.w * val.w : 0.f;
-            red[i][1] = (float)W * (dxs.x * tg.x + dxs.y * tg.y + dxs.z * tg.z + dxs.w * tg.w);
-            red[i][2] = (float)H * (dys.x * tg.x + dys.y * tg.y + dys.z * tg.z + dys.w * tg.w);
-          }
-          if constexpr (!GATHER) {
-            // scatter-only instantiation: grad_loc / grad_attn come from the gather-only kernel
-          } else if constexpr (G == 8 && NB == 4) {
-            float tot[3];
-            const int sidx = reduce_scatter_g8_p4(red, j, tot);
-            if ((j & 1) == 0) {
-              const long long wi = row * NS + l * P + p0 + sidx;
-              gattn[wi] = tot[0];
-              *reinterpret_cast<float2*>(gloc + wi * 2) = make_float2(tot[1], tot[2]);
-            }
-          } else {
-#pragma unroll
-            for (int i = 0; i < NB; ++i) {
-              const float ga = group_sum<G>(red[i][0]), gx = group_sum<G>(red[i][1]), gy = group_sum<G>(red[i][2]);
-              if (j == 0) {
-                const long long wi = row * NS + l * P + p0 + i;
-                gattn[wi] = ga;
-                *reinterpret_cast<float2*>(gloc + wi * 2) = make_float2(gx, gy);
-              }
-            }
-          }
-        }
-      }
-      __syncthreads();
-    }
-    if (pass == npass - 1) {
-      // flush this level's window: one global atomic per touched (pixel, channel)
-      float* gl = gvalue + (long long)b * S * MD + (long long)lvlS[l] * MD + m * D;
-      for (int i = tid; i < ww * wh * D; i += 256) {
-        const float v = (float)acc[i];
-        if (v != 0.f) {
-          const int pp = i / D, slot = (i % D) / G, jj = i % G;
-          const int c = jj + G * ((slot - pp) & 3);                  // undo the bank-group swizzle
-          atomicAdd(gl + ((long long)(oy + pp / ww) * W + ox + pp % ww) * MD + c, v);
-        }
-      }
-      __syncthreads();
     }
   }
 }
@@ -834,48 +513,6 @@ __global__ __launch_bounds__(256) void msda_bwd_generic(const T* __restrict__ va
   }
 }
 
-// ------------------------------------------------------------------------------------------------------
-// Host side of the tiled backward: window sizes per (query level, destination level) from the level shapes.
-// margin: how far (in destination pixels) beyond the patch's own footprint the window extends; the origin is
-// data-driven, so the margin only has to cover the SPREAD of the offsets, not their common shift.
-inline bool make_tile_geom(const int64_t* sh, int L, int D, int rows_per_pass, int P, TileGeom& g, size_t& lds_bytes) {
-  const int margin = 3;
-#ifndef MSDA_LDS_CAP_KB
-#define MSDA_LDS_CAP_KB 52
-#endif
-  const size_t cap = MSDA_LDS_CAP_KB * 1024;            // LDS budget per workgroup: 52 KB -> 3 workgroups (12 waves) per CU
-  const size_t rec_bytes = (size_t)rows_per_pass * P * sizeof(TileRec);
-  g.L = L;
-  int base = 0;
-  int max_pix = 0;
-  for (int lq = 0; lq < L; ++lq) {
-    const int Hq = (int)sh[2 * lq], Wq = (int)sh[2 * lq + 1];
-    if (Hq <= 0 || Wq <= 0) return false;
-    g.tile_base[lq] = base;
-    g.tiles_x[lq] = (Wq + kTile - 1) / kTile;
-    base += g.tiles_x[lq] * ((Hq + kTile - 1) / kTile);
-    int off = 0;
-    for (int l = 0; l < L; ++l) {
-      const int H = (int)sh[2 * l], W = (int)sh[2 * l + 1];
-      const int fw = (std::min(kTile, Wq) * W + Wq - 1) / Wq, fh = (std::min(kTile, Hq) * H + Hq - 1) / Hq;   // patch footprint
-      int ww = std::min(W, fw + 2 * margin + 2), wh = std::min(H, fh + 2 * margin + 2);
-      while ((size_t)ww * wh * D * sizeof(double) + rec_bytes > cap) {     // shrink to the budget (more fallback atomics, same result)
-        if (ww >= wh && ww > 1) --ww; else if (wh > 1) --wh; else return false;
-      }
-      g.win_w[lq][l] = ww;
-      g.win_h[lq][l] = wh;
-      g.win_off[lq][l] = 0;
-      off += ww * wh;
-      max_pix = std::max(max_pix, ww * wh);
-    }
-    g.win_pixels[lq] = off;
-  }
-  g.tile_base[L] = base;
-  g.ntiles = base;
-  lds_bytes = rec_bytes + (size_t)max_pix * D * sizeof(double);
-  return lds_bytes <= cap;
-}
-
 inline int fast_group(int D) {
   if (D % 4) return 0;
   const int g = D / 4;
@@ -901,7 +538,7 @@ inline int check_common(const void* a, const void* b, const void* c, const void*
   return 0;
 }
 
-// OCPG_MSDA_COL=0 keeps the row / tiled kernels (A/B timing and parity of the older paths); default: column kernels
+// OCPG_MSDA_COL=0 keeps the row kernel with its atomic scatter for every shape (A/B timing and parity); default: column kernels
 inline bool col_enabled() {
   const char* e = std::getenv("OCPG_MSDA_COL");      // read per call: tests toggle it in-process
   return !(e && e[0] == '0');
@@ -919,6 +556,11 @@ inline int launch_status() {
   return e == hipSuccess ? 0 : -(int)e;
 }
 
+// The column scatter's geometry: 8 x 16 query tiles on the finest level, LDS window margins kScatterMarginLo / kMarginHi (msda_col.h).
+inline bool scatter_col_geom(const int64_t* shapes_host, int L, int S, int M, int P, ocpg_col::ColGeom& cg) {
+  return ocpg_col::make_col_geom(shapes_host, L, S, M, P, 8, 16, cg, ocpg_col::kScatterMarginLo, ocpg_col::kMarginHi);
+}
+
 // ---- the two halves of the self-attention backward (also exported on their own: include/ocpg_hip.h) -----------------
 // 1 = launched, 0 = shape not served by these kernels
 // go_dtype: storage of grad_out (0 = float32, 1 = bfloat16, 2 = float16: the _h16 entry points of msda_h16.hip)
@@ -932,9 +574,7 @@ inline int launch_bwd_value_col(const float* loc, const float* attn, const void*
   const char* te = std::getenv("OCPG_MSDA_TILE");
   if (te && te[0] == '1' && ocpg_tile::bwd_value_tile(loc, attn, grad_out, shapes_host, N, S, M, D, L, P, grad_value, st, nullptr, 0, go_dtype)) return 1;
   ocpg_col::ColGeom cg;
-  const char* tw = std::getenv("OCPG_MSDA_TILEW");      // experiment switch: scatter tile width on the finest level
-  static const int mlo = [] { const char* e = std::getenv("OCPG_MSDA_MARGIN_LO"); return e ? std::atoi(e) : ocpg_col::kScatterMarginLo; }();    // A/B
-  if (!ocpg_col::make_col_geom(shapes_host, L, S, M, P, 8, tw ? std::atoi(tw) : 16, cg, mlo, ocpg_col::kMarginHi)) return 0;
+  if (!scatter_col_geom(shapes_host, L, S, M, P, cg)) return 0;
   return ocpg_col::bwd_scatter_col(loc, attn, grad_out, N, S, M, D, P, cg, grad_value, st, nullptr, 0, go_dtype);
 }
 
@@ -968,9 +608,8 @@ int ocpg_msda::bwd_value_sel(const float* loc, const float* attn, const void* gr
     //   ring + N(0, 3 px) + 5 % far       9.3 %   432               12.5 %   361
     static const int to_tile = [] { const char* e = std::getenv("OCPG_MSDA_SEL_TO_TILE"); return e ? std::atoi(e) : 6; }();
     static const int to_col = [] { const char* e = std::getenv("OCPG_MSDA_SEL_TO_COL"); return e ? std::atoi(e) : 6; }();
-    static const int mlo = [] { const char* e = std::getenv("OCPG_MSDA_MARGIN_LO"); return e ? std::atoi(e) : ocpg_col::kScatterMarginLo; }();
     ocpg_col::ColGeom cg;
-    if (ocpg_col::make_col_geom(shapes_host, L, S, M, P, 8, 16, cg, mlo, ocpg_col::kMarginHi) && ocpg_col::select_supported(cg, D, P) &&
+    if (scatter_col_geom(shapes_host, L, S, M, P, cg) && ocpg_col::select_supported(cg, D, P) &&
         ocpg_tile::tile_supported(shapes_host, N, L, S, M, P, D)) {
       if (ocpg_col::bwd_scatter_col(loc, attn, grad_out, N, S, M, D, P, cg, grad_value, st, sel_state, to_tile, go_dtype) != 2) return -2001;
       if (!ocpg_tile::bwd_value_tile(loc, attn, grad_out, shapes_host, N, S, M, D, L, P, grad_value, st, sel_state, to_col, go_dtype)) return -2002;
@@ -994,12 +633,6 @@ int ocpg_msda::bwd_value_sel(const float* loc, const float* attn, const void* gr
     default: KERNEL<64><<<grid, 256, lds, st>>>(__VA_ARGS__); break;                             \
   }
 
-#define FAST_DISPATCH_GATHER(G_, GRID_, LDS_)                                                                                     \
-  switch (G_) {                                                                                                                 \
-    case 4: msda_bwd_fast<4, false><<<GRID_, 256, LDS_, st>>>(value, shapes, level_start, loc, attn, grad_out, S, M, L, Lq, P, rows, grad_value, grad_loc, grad_attn); break; \
-    default: msda_bwd_fast<8, false><<<GRID_, 256, LDS_, st>>>(value, shapes, level_start, loc, attn, grad_out, S, M, L, Lq, P, rows, grad_value, grad_loc, grad_attn); break; \
-  }
-
 extern "C" {
 
 const char* ocpg_hip_version(void) { return "ocpg_hip gfx950 r4"; }
@@ -1020,11 +653,7 @@ int ocpg_msda_fwd_f32(const float* value, const int64_t* shapes, const int64_t* 
   const size_t rec_bytes = (size_t)L * P * sizeof(SampleRec);
   if (G && L <= kMaxLevels && (256 / G) * rec_bytes <= 48 * 1024 && (long long)S * M * D < (1LL << 31)) {
     const int rpb = 256 / G;
-#ifndef MSDA_ROW_MAJOR
     const unsigned grid = (unsigned)((((long long)N * Lq + rpb - 1) / rpb) * M);
-#else
-    const unsigned grid = (unsigned)((rows + rpb - 1) / rpb);
-#endif
     const size_t lds = rpb * rec_bytes;
     // (a mask-free variant with validity folded into the weights, as in msda_bwd_gather_row, measured 109 vs 100 us: the
     //  forward is bound by the 16-B-per-lane gather path, not by its selects)
@@ -1066,54 +695,13 @@ int ocpg_msda_bwd_f32(const float* value, const int64_t* shapes, const int64_t* 
     // and the row gather (grad_loc, grad_attn; reads value too).  (Running them on two streams was measured: 405 vs
     // 415 us -- each fills the chip on its own -- so both stay on the caller's stream.)
     if (launch_bwd_value_col(loc, attn, grad_out, shapes_host, N, S, M, D, L, Lq, P, grad_value, st)) {
-      if (launch_bwd_locattn_row(value, shapes, level_start, loc, attn, grad_out, N, S, M, D, L, Lq, P, grad_loc, grad_attn, st))
-        return launch_status();
-      // (not reachable: the scatter accepts a subset of the gather's shapes) finish with the round-1 gather-only kernel
-      const unsigned ggrid = (unsigned)((((long long)N * Lq + rpb - 1) / rpb) * M);
-      FAST_DISPATCH_GATHER(G, ggrid, rpb * rec_bytes)
+      // the scatter takes G in {4, 8} only and the two row kernels' LDS records have one size, so the gather takes whatever the
+      // enclosing condition took; a refusal here would be a bug, reported like a family that refuses after the geometry checks
+      static_assert(sizeof(GatherRec) == sizeof(SampleRec), "launch_bwd_locattn_row must accept what the fast-path condition accepted");
+      if (!launch_bwd_locattn_row(value, shapes, level_start, loc, attn, grad_out, N, S, M, D, L, Lq, P, grad_loc, grad_attn, st)) return -2001;
       return launch_status();
     }
-    TileGeom geo;
-    size_t tiled_lds = 0;
-    if (shapes_host && Lq == S && L <= kMaxTileLevels && G >= 4 && G <= 16 && make_tile_geom(shapes_host, L, D, rpb, P, geo, tiled_lds)) {
-      const unsigned grid = (unsigned)((long long)N * M * geo.ntiles);
-      const size_t lds = tiled_lds;
-#ifndef MSDA_SPLIT
-#define MSDA_SPLIT 0      // 1: scatter-only tiled kernel (grad_value) + gather-only row kernel (grad_loc / grad_attn): measured 746 us vs 701 us for the single kernel (0)
-#endif
-#ifndef MSDA_NB
-#define MSDA_NB 2
-#endif
-#if MSDA_SPLIT
-#define TILED_LAUNCH(G_, NB_) msda_bwd_tiled<G_, NB_, false><<<grid, 256, lds, st>>>(value, shapes, level_start, loc, attn, grad_out, S, M, P, geo, grad_value, grad_loc, grad_attn)
-#else
-#define TILED_LAUNCH(G_, NB_) msda_bwd_tiled<G_, NB_, true><<<grid, 256, lds, st>>>(value, shapes, level_start, loc, attn, grad_out, S, M, P, geo, grad_value, grad_loc, grad_attn)
-#endif
-      const bool b4 = (P % MSDA_NB) == 0;
-      switch (G) {
-        case 4: if (b4) TILED_LAUNCH(4, MSDA_NB); else TILED_LAUNCH(4, 1); break;
-        case 8: if (b4) TILED_LAUNCH(8, MSDA_NB); else TILED_LAUNCH(8, 1); break;
-        default: if (b4) TILED_LAUNCH(16, MSDA_NB); else TILED_LAUNCH(16, 1); break;
-      }
-#if MSDA_SPLIT
-      {   // the gather side at full occupancy (no LDS window, ~half the registers): same row kernel as the cross-attention path
-        const unsigned ggrid = (unsigned)((((long long)N * Lq + rpb - 1) / rpb) * M);
-        const size_t glds = rpb * rec_bytes;
-        switch (G) {
-          case 4: msda_bwd_fast<4, false><<<ggrid, 256, glds, st>>>(value, shapes, level_start, loc, attn, grad_out, S, M, L, Lq, P, rows, grad_value, grad_loc, grad_attn); break;
-          case 8: msda_bwd_fast<8, false><<<ggrid, 256, glds, st>>>(value, shapes, level_start, loc, attn, grad_out, S, M, L, Lq, P, rows, grad_value, grad_loc, grad_attn); break;
-          default: msda_bwd_fast<16, false><<<ggrid, 256, glds, st>>>(value, shapes, level_start, loc, attn, grad_out, S, M, L, Lq, P, rows, grad_value, grad_loc, grad_attn); break;
-        }
-      }
-#endif
-#undef TILED_LAUNCH
-      return launch_status();
-    }
-#ifndef MSDA_ROW_MAJOR
     const unsigned grid = (unsigned)((((long long)N * Lq + rpb - 1) / rpb) * M);
-#else
-    const unsigned grid = (unsigned)((rows + rpb - 1) / rpb);
-#endif
     const size_t lds = rpb * rec_bytes;
     FAST_DISPATCH(G, msda_bwd_fast, value, shapes, level_start, loc, attn, grad_out, S, M, L, Lq, P, rows, grad_value, grad_loc,
                   grad_attn)
@@ -1127,14 +715,7 @@ int ocpg_msda_bwd_f32(const float* value, const int64_t* shapes, const int64_t* 
 
 int ocpg_msda_bwd_value_f32(const float* loc, const float* attn, const float* grad_out, int N, int S, int M, int D, int L, int Lq, int P,
                             float* grad_value, const int64_t* shapes_host, void* stream) {
-  if (N < 0 || S <= 0 || M <= 0 || D <= 0 || L <= 0 || Lq < 0 || P <= 0) return -1006;
-  if ((long long)N * Lq == 0) return 0;
-  if (!loc) return -1001;
-  if (!attn) return -1002;
-  if (!grad_out) return -1003;
-  if (!grad_value) return -1011;
-  if (!launch_bwd_value_col(loc, attn, grad_out, shapes_host, N, S, M, D, L, Lq, P, grad_value, (hipStream_t)stream)) return -2000;
-  return launch_status();
+  return ocpg_msda_bwd_value_sel_f32(loc, attn, grad_out, N, S, M, D, L, Lq, P, grad_value, shapes_host, nullptr, stream);
 }
 
 // grad_value with per-call path selection (include/ocpg_hip.h).  Both paths' kernels are launched; the call site's state decides on the

@@ -47,19 +47,6 @@ __device__ __forceinline__ unsigned udiv(unsigned n, unsigned d, unsigned m) {  
 // barrier for LDS hand-offs only (does not drain this wave's global stores / atomics)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-#ifdef EXP_STAMPS
-// Diagnostic build only (never shipped): per-phase cycle sums of wave 0 of every workgroup ([0..7] tile kernel, [8..15] coarse),
-// kept in registers and added to memory ONCE per workgroup (a global atomic per stamp perturbs what it measures).
-__device__ unsigned long long g_tstamps[16];
-#define STAMP_INIT unsigned tacc_[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long tprev = __builtin_amdgcn_s_memtime()
-#define STAMP(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); tacc_[(k) & 7] += (unsigned)(t_ - tprev); tprev = t_; } while (0)
-#define STAMP_FLUSH(base) do { if (tid == 0) { for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&g_tstamps[(base) + i_], (unsigned long long)tacc_[i_]); } } while (0)
-#else
-#define STAMP(k) do { } while (0)
-#define STAMP_INIT do { } while (0)
-#define STAMP_FLUSH(base) do { } while (0)
-#endif
-
 struct __attribute__((aligned(8))) Item {
   float w;   // bilinear weight * attention weight
   int q;     // float offset of the query's staged grad_out row
@@ -116,8 +103,8 @@ __device__ __forceinline__ void sum_list(const Item* __restrict__ lst, int n, co
 // ======================================================================================================================
 // A round of either kernel = NB entries (an entry = one query at one destination level: its 4 points), TWO threads per entry
 // (2 points = 8 corner contributions each), so a round bins at most 16 * NB items and stages NB grad_out rows: 32 KB of LDS per
-// workgroup for NB = 128 -> 4 workgroups (16 waves) per CU; every phase is bound by LDS / memory LATENCY, not throughput (stamps,
-// tools/stamps_tile.py), so occupancy and batched independent LDS operations are what pay.
+// workgroup for NB = 128 -> 4 workgroups (16 waves) per CU; every phase is bound by LDS / memory LATENCY, not throughput (phase stamps, since removed:
+// DESIGN.md section 4.2b), so occupancy and batched independent LDS operations are what pay.
 constexpr int NB = NT / 2;                                // entries per round
 constexpr int kItems = NB * 16;                           // corner contributions of one round at most
 constexpr int kListMax = 2048;                            // compacted (query, level) entries of a tile at most (= its candidates)
@@ -225,7 +212,6 @@ __global__ __launch_bounds__(NT, 4) void k_gv_tile(const float* __restrict__ loc
   const int b = (int)udiv(bt, tab.ntiles, tab.m_ntiles), tile = bt - b * tab.ntiles;
   const int ty = (int)udiv(tile, tab.ntx, tab.m_ntx), tx = tile - ty * tab.ntx;
   const int L = tab.L, LA = tab.LA;
-  STAMP_INIT;
   if (tid < 192) sh.cnt[tid] = 0;
   if (tid == 192) sh.nlist = 0;
   if (tid < LA * kLM) {
@@ -260,7 +246,6 @@ __global__ __launch_bounds__(NT, 4) void k_gv_tile(const float* __restrict__ loc
   __syncthreads();
   const int nb = sh.pixbase[LA];
   const long long rowb = (long long)b * S;
-  STAMP(0);
   // ---- prefilter: which candidates have a corner inside the footprint?  (no atomics, no barrier: position arithmetic only) ----
   for (int l = 0; l < LA; ++l) {
     const int H = tab.H[l], W = tab.W[l];
@@ -304,7 +289,6 @@ __global__ __launch_bounds__(NT, 4) void k_gv_tile(const float* __restrict__ loc
   }
   __syncthreads();
   const int nent = sh.nlist;
-  STAMP(1);
   float4 acc[NPA];
 #pragma unroll
   for (int k = 0; k < NPA; ++k) acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -328,17 +312,12 @@ __global__ __launch_bounds__(NT, 4) void k_gv_tile(const float* __restrict__ loc
 #pragma unroll
     for (int u = 0; u < NB / NGRP; ++u) *reinterpret_cast<float4*>(gs + (grp + u * NGRP) * D + 4 * j) = gq[u];
     lds_barrier();
-    STAMP(2);
     if (tid < 64) wave_scan_bins<3>(sh.cnt, sh.start, lane);
     lds_barrier();
-    STAMP(3);
     drop_items(key, wv, (tid >> 1) * D, sh.start, items);
     lds_barrier();
-    STAMP(4);
     sum_pixels<NPA>(grp, j, nb, sh.cnt, sh.start, items, gs, acc);
-    STAMP(5);
     lds_barrier();
-    STAMP(6);
   }
   // ---- every pixel of the footprint is written exactly once ---------------------------------------------------------------
 #pragma unroll
@@ -353,8 +332,6 @@ __global__ __launch_bounds__(NT, 4) void k_gv_tile(const float* __restrict__ loc
       *reinterpret_cast<float4*>(gvalue + ((rowb + gp) * M + m) * D + 4 * j) = acc[k];
     }
   }
-  STAMP(7);
-  STAMP_FLUSH(0);
 }
 
 // ======================================================================================================================
@@ -393,7 +370,6 @@ __global__ __launch_bounds__(NT, NPX <= 10 ? 3 : 1) void k_gv_coarse(const float
   const long long rowb = (long long)b * S;
   float* gvb = gvalue + rowb * MD + m * D;
   const int half = tid & 1, ql = tid >> 1;             // two threads per query: points {0,1} and {2,3}
-  STAMP_INIT;
   __syncthreads();
 
   const int nbatch = (nq + NB - 1) / NB;
@@ -419,7 +395,6 @@ __global__ __launch_bounds__(NT, NPX <= 10 ? 3 : 1) void k_gv_coarse(const float
       for (int u = 0; u < NB / NGRP; ++u) *reinterpret_cast<float4*>(gs + (grp + u * NGRP) * D + 4 * j) = gq[u];
     }
     lds_barrier();
-    STAMP(8);
     // ---- far corners of the fine levels: straight to memory (after k_gv_tile's stores: stream order) -------------------------
     if (LA > 0) {
       int lq = 0;
@@ -475,7 +450,6 @@ __global__ __launch_bounds__(NT, NPX <= 10 ? 3 : 1) void k_gv_coarse(const float
         }
       }
     }
-    STAMP(9);
     // ---- the coarse levels: bin, sum in registers (their points are loaded together, after the fine ones are dead) ----------------
 #pragma unroll
     for (int l = kLA; l < kLM; ++l) pts[l] = load_pts2(loc, attn, row, L, min(l, L - 1), half);
@@ -491,17 +465,12 @@ __global__ __launch_bounds__(NT, NPX <= 10 ? 3 : 1) void k_gv_coarse(const float
         float wv[8];
         bin_points(pts[l], active, H, W, 0, H, 0, W, W, tab.offB[l], sh.cnt, key, wv);
         lds_barrier();
-        STAMP(10);
         if (tid < 64) wave_scan_bins<NPX / 2>(sh.cnt, sh.start, lane);
         lds_barrier();
-        STAMP(11);
         drop_items(key, wv, ql * D, sh.start, items);
         lds_barrier();
-        STAMP(12);
         sum_pixels<NPX>(grp, j, nb, sh.cnt, sh.start, items, gs, acc);
-        STAMP(13);
         lds_barrier();
-        STAMP(14);
       }
     }
     if (LA == L) lds_barrier();      // (uniform) no coarse round followed: the far pass's reads of gs must finish before the next batch stages
@@ -543,8 +512,6 @@ __global__ __launch_bounds__(NT, NPX <= 10 ? 3 : 1) void k_gv_coarse(const float
     __syncthreads();
     if (tid == 0) ocpg_col::sel_report(sel, sel_far, sel_seen);
   }
-  STAMP(15);
-  STAMP_FLUSH(8);
 }
 
 template <typename Kn>
@@ -686,14 +653,3 @@ int bwd_value_tile(const float* loc, const float* attn, const void* gout, const 
 }
 
 }  // namespace ocpg_tile
-
-#ifdef EXP_STAMPS
-extern "C" int ocpg_debug_stamps_tile(unsigned long long* out16, int reset) {
-  if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(ocpg_tile::g_tstamps), 16 * sizeof(unsigned long long)) != hipSuccess) return -1;
-  if (reset) {
-    unsigned long long z[16] = {};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(ocpg_tile::g_tstamps), z, sizeof(z)) != hipSuccess) return -2;
-  }
-  return 0;
-}
-#endif

@@ -221,7 +221,7 @@ def test_self_attention_kernels_vs_c_oracle(dev, shapes_l):
     """Forward + backward on locality-structured inputs, element-wise against the C oracle (one frame keeps the CPU side
     to seconds), for every path that serves Lq == S: default (row forward, column scatter + row gather backward), the
     output-tiled grad_value kernels (round 3, csrc/msda_tile.hip, OCPG_MSDA_TILE=1), the LDS-window forward (OCPG_MSDA_FWD=col)
-    and the round-1 kernels (OCPG_MSDA_COL=0).  The inputs hold samples within the tile margin, beyond it (far corners: atomics of the
+    and the round-1 row kernel with its atomic scatter (OCPG_MSDA_COL=0).  The inputs hold samples within the tile margin, beyond it (far corners: atomics of the
     coarse kernel) and outside the map."""
     from oracle import msda as om
     from ocpg_amd.models.ops.functions import ms_deform_attn_backward, ms_deform_attn_forward
@@ -264,9 +264,35 @@ def test_single_level_scatter_by_dispatch_vs_c_oracle(dev, D, P):
     assert torch.allclose(ga.cpu(), oga, rtol=1e-3, atol=1e-4)
 
 
+@pytest.mark.parametrize("M,D,P", [(2, 64, 4), (4, 32, 8)], ids=["D64_P4", "D32_P8"])
+def test_self_attention_refused_by_column_scatter_vs_c_oracle(dev, M, D, P):
+    """Self-attention calls with host shapes that the column scatter does not take reach the row kernel with its atomic
+    scatter, `msda_bwd_fast<G>`, by dispatch, with no environment override (they went to the fp64-LDS tiled backward before
+    that kernel was removed): forward + backward element-wise against the C oracle, at the tolerances of
+    test_self_attention_kernels_vs_c_oracle.  (M, D, P) = (2, 64, 4) is refused by the group size (the column kernels are
+    D = 16 / 32 only); (4, 32, 8) is refused by `scatter_threads`: an 8 x 16 tile of the 16 x 24 level plus its share of the
+    8 x 12 level is more than 128 queries, and with 8 points each they exceed the 768 samples a level pass bins.  A kernel
+    trace of both cases shows msda_bwd_tiled before the removal and msda_bwd_fast after it."""
+    from oracle import msda as om
+    from ocpg_amd.models.ops.functions import ms_deform_attn_backward, ms_deform_attn_forward
+    value, shapes, ls, loc, attn, go = _local_inputs(dev, 1, [(16, 24), (8, 12)], M=M, D=D, P=P)
+    oc = om.msda_c_forward(value, shapes, ls, loc, attn)
+    ogv, ogl, oga = om.msda_c_backward(value, shapes, ls, loc, attn, go)
+    dv, dl, da, dg = (t.to(dev) for t in (value, loc, attn, go))
+    ds, dls = shapes.to(dev), ls.to(dev)
+    ds._ocpg_host = shapes
+    out = ms_deform_attn_forward(dv, ds, dls, dl, da)
+    gv, gl, ga = ms_deform_attn_backward(dv, ds, dls, dl, da, dg)
+    assert torch.allclose(out.cpu(), oc, rtol=1e-4, atol=1e-5)
+    assert torch.allclose(gv.cpu(), ogv, rtol=1e-3, atol=1e-4)
+    assert (gl.cpu() - ogl).abs().max() <= 2e-5 * ogl.abs().max()
+    assert torch.allclose(ga.cpu(), oga, rtol=1e-3, atol=1e-4)
+
+
 def test_self_attention_backward_paths_agree_at_bench_size(dev):
-    """N = 10 frames (what bench.py runs: 2 clips x 5 frames): column scatter + row gather against the round-1 tiled
-    kernel (itself pinned to the oracle above), plus the adjointness <out, go> == <value, grad_value>."""
+    """N = 10 frames (what bench.py runs: 2 clips x 5 frames): column scatter + row gather against the round-1 row kernel
+    with its atomic scatter (OCPG_MSDA_COL=0; itself pinned to the oracle above), plus the adjointness
+    <out, go> == <value, grad_value>."""
     from ocpg_amd.models.ops.functions import ms_deform_attn_backward, ms_deform_attn_forward
     value, shapes, ls, loc, attn, go = (t.to(dev) if i != 1 else t for i, t in
                                         enumerate(_local_inputs(dev, 10, [(48, 80), (24, 40), (12, 20), (6, 10)], seed=9)))

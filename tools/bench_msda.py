@@ -1,6 +1,7 @@
 """Micro-benchmark + A/B parity of the MSDeformAttn kernels at BASELINE config #2 encoder/decoder shapes (HIP events).
 
-OCPG_MSDA_COL=0/1 is toggled in-process: the column-tile kernels (default) against the row / tiled kernels of round 1.
+OCPG_MSDA_COL=0/1 is toggled in-process: the column-tile kernels (default) against the row kernels of round 1
+(forward msda_fwd_fast; backward msda_bwd_fast, gather and atomic scatter in one kernel).
 Offsets: "ring" = the reference's initialisation (ms_deform_attn.py:64-78: 1..P pixels along the head's direction),
 "ring+n" = the same plus gaussian noise (sigma 1.5 px) and 2 % far outliers, "uniform" = anywhere in the map.
 """
