@@ -735,6 +735,23 @@ int ocpg_graph_stats(void* hip_graph, long long* out9);
  * cap are written).  Host-to-device nodes re-read their host source on every replay. */
 int ocpg_graph_memcpy_nodes(void* hip_graph, long long* out, int cap);
 
+/* The text gate of VisionLanguageFusionModule (models/segmentation.py:95-113) with its two 256x256 projections folded into the text
+ * side (csrc/text_gate.hip): out[b, l, :] = x[b, l, :] * round16(sum_n P[n] V'[b, n, :] + bo), P = per-head
+ * softmax over the keys of scale * (round16(x[b, l, :]) . K'[b, n, :] + c[b, n]).  x / g / out / dx [B, L, 256] fp32; K' / V'
+ * [B, 8 Lk, 256] in the 16-bit type, c [B, 8 Lk] and bo [256] fp32, rows KEY-major (n = key * 8 + head); key_pad [B, Lk] bytes,
+ * non-zero = ignore this key, or NULL.  dtype 1 bf16 / 2 fp16 (the type of K' / V' and of every rounding).
+ * Backward: dx, and part [ocpg_text_gate_splits(L)][B][W] fp32 with W = 2 NP 256 + NP + 256, NP = ocpg_text_gate_rows(Lk): per
+ * workgroup partial sums over token ranges of dK' [NP][256], dV' [NP][256], dc [NP], dbo [256] (rows past 8 Lk are zero); every
+ * element is written, the caller adds the partials over the first axis.  ws: 2 * B * L * NP 16-bit elements of scratch.  No atomics.
+ * Served: C = 256, H = 8, 1 <= Lk <= 16, B <= 65535, 16-byte-aligned pointers; anything else returns -2000 before any launch. */
+int ocpg_text_gate_rows(int Lk);
+int ocpg_text_gate_splits(int L);
+int ocpg_text_gate_fwd_h16(const float* x, const void* Kp, const void* Vp, const float* c, const float* bo, const unsigned char* key_pad,
+                           float scale, int B, int L, int C, int H, int Lk, float* out, int dtype, void* stream);
+int ocpg_text_gate_bwd_h16(const float* x, const float* g, const void* Kp, const void* Vp, const float* c, const float* bo,
+                           const unsigned char* key_pad, float scale, int B, int L, int C, int H, int Lk, float* dx, float* part, void* ws,
+                           int dtype, void* stream);
+
 /* library / build identification: returns e.g. "ocpg_hip gfx950 r1" */
 const char* ocpg_hip_version(void);
 

@@ -198,24 +198,39 @@ class OCPG(nn.Module):
             return NestedTensor(self.text_proj(feats), pad), self.sentence_proj(sentence)
         raise ValueError("Please mask sure the caption is a list of string")
 
-    def _fuse_level(self, l, src, b, t, text_words, text_pad, text_pos, high_filter):
-        """LFM -> text gating -> LFM on one level ([(b t), C, h, w])."""
+    def _gate_token_major(self, src, b, t, text_words, text_pad, text_pos):
+        """The text gate on the reference's token-major layout: [(b t), C, h, w] -> [(b t), C, h, w]."""
         n, c, h, w = src.shape
-        src, high_filter = self.input_fft[l](src, high_filter)
-        if CL_FUSE and GATE_BF and src.is_cuda and src.permute(0, 2, 3, 1).is_contiguous():
-            # the channels-last map IS the token list [b, (t h w), c]: gate it where it lies (no token-major round trip)
-            out = self.fusion_module.forward_batch_first(src.permute(0, 2, 3, 1).reshape(b, t * h * w, c), text_words, text_pad, text_pos)
-            if out is not None:
-                return self.input_fft_post[l](out.view(b * t, h, w, c).permute(0, 3, 1, 2), high_filter)
         vis = src.view(b, t, c, h, w).permute(1, 3, 4, 0, 2)                      # t h w b c
         vis = self.fusion_module(visual=vis, text=text_words, text_key_padding_mask=text_pad, text_pos=text_pos, visual_pos=None)
         if CL_FUSE and vis.is_cuda:
             # [(b t), c, h, w] in channels-last memory: ONE copy out of the token-major layout (the LFM's transforms and the transformer's
             # flatten(2).transpose(1, 2) both read channels-last; NCHW here cost a second transposing copy in each of them)
-            src = vis.view(t, h, w, b, c).permute(3, 0, 1, 2, 4).reshape(b * t, h, w, c).permute(0, 3, 1, 2)
-        else:
-            src = vis.view(t, h, w, b, c).permute(3, 0, 4, 1, 2).reshape(b * t, c, h, w)
-        return self.input_fft_post[l](src, high_filter)
+            return vis.view(t, h, w, b, c).permute(3, 0, 1, 2, 4).reshape(b * t, h, w, c).permute(0, 3, 1, 2)
+        return vis.view(t, h, w, b, c).permute(3, 0, 4, 1, 2).reshape(b * t, c, h, w)
+
+    def _fuse_level(self, l, src, b, t, text_words, text_pad, text_pos, high_filter, shared=None):
+        """LFM -> text gating -> LFM on one level ([(b t), C, h, w]).  shared: this forward's dict for what its levels have in common (the
+        fused gate's text-side operands)."""
+        n, c, h, w = src.shape
+        src, high_filter = self.input_fft[l](src, high_filter)
+        if CL_FUSE and (GATE_BF or self.fusion_module.fused_gate_enabled()) and src.is_cuda and src.permute(0, 2, 3, 1).is_contiguous():
+            # the channels-last map IS the token list [b, (t h w), c]: the fused gate (csrc/text_gate.hip) takes its backward there
+            # whenever it serves the call (the forward stays the token-major one below, bit for bit, unless OCPG_TEXT_GATE_FUSED=fwd);
+            # the unfused gate on that view only on request (OCPG_GATE_BF)
+            tokens = src.permute(0, 2, 3, 1).reshape(b, t * h * w, c)
+            out = None
+            if self.fusion_module.fused_gate_serves(tokens, text_words):
+                def token_major(tok):
+                    return self._gate_token_major(tok.view(b * t, h, w, c).permute(0, 3, 1, 2), b, t, text_words, text_pad,
+                                                  text_pos).permute(0, 2, 3, 1).reshape(b, t * h * w, c)
+                out = self.fusion_module.forward_tokens(tokens, text_words, text_pad, text_pos, unfused=None if GATE_BF else token_major,
+                                                        shared=shared)
+            elif GATE_BF:
+                out = self.fusion_module.forward_batch_first(tokens, text_words, text_pad, text_pos)
+            if out is not None:
+                return self.input_fft_post[l](out.view(b * t, h, w, c).permute(0, 3, 1, 2), high_filter)
+        return self.input_fft_post[l](self._gate_token_major(src, b, t, text_words, text_pad, text_pos), high_filter)
 
     def forward(self, samples, captions, targets):
         """samples: NestedTensor([B,T,3,H,W], mask [B,T,H,W]) or list of [T,3,H,W]; captions: list[str] (or
@@ -247,17 +262,18 @@ class OCPG(nn.Module):
         # ---- spectrum-guided cross-modal fusion (last three backbone levels + one extra stride-2 level) ----
         srcs, masks, poses = [], [], []
         high_filter = None
+        shared = {}         # lives as long as this forward: nothing of its autograd graph is cached beyond it
         n_scales = 3
         for l, (feat, pos_l) in enumerate(zip(features[-n_scales:], visual_pos[-n_scales:])):
             src, mask = feat.decompose()
             assert mask is not None
-            src, high_filter = self._fuse_level(l, self.input_proj[l](src), b, t, text_words, text_pad, text_pos, high_filter)
+            src, high_filter = self._fuse_level(l, self.input_proj[l](src), b, t, text_words, text_pad, text_pos, high_filter, shared)
             srcs.append(src), masks.append(mask), poses.append(pos_l)
         for l in range(len(srcs), self.num_feature_levels):
             src = self.input_proj[l](features[-1].tensors if l == n_scales else srcs[-1])
             mask = resize_mask(samples.mask, src.shape[-2:])
             pos_l = self.backbone[1](NestedTensor(src, mask)).to(src.dtype)
-            src, high_filter = self._fuse_level(l, src, b, t, text_words, text_pad, text_pos, high_filter)
+            src, high_filter = self._fuse_level(l, src, b, t, text_words, text_pad, text_pos, high_filter, shared)
             srcs.append(src), masks.append(mask), poses.append(pos_l)
 
         # ---- deformable transformer ----

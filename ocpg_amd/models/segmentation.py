@@ -11,6 +11,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .attention import MultiheadAttention
+from .ops.functions import text_gate_func
 
 
 class VisionLanguageFusionModule(nn.Module):
@@ -26,6 +27,28 @@ class VisionLanguageFusionModule(nn.Module):
         q = visual if visual_pos is None else visual + visual_pos
         k = text if text_pos is None else text + text_pos
         return visual * self.multihead_attn(q, k, text, key_padding_mask=text_key_padding_mask)
+
+    @staticmethod
+    def fused_gate_enabled():
+        return text_gate_func.ENABLED
+
+    def fused_gate_serves(self, visual, text):
+        """True when forward_tokens(visual [b, L, c], text, ...) runs as the fused gate (csrc/text_gate.hip)."""
+        return text_gate_func.served(self.multihead_attn, visual, text)
+
+    def forward_tokens(self, visual, text, text_key_padding_mask=None, text_pos=None, unfused=None, shared=None):
+        """visual [b, L, c] (the channels-last map's own memory) -> [b, L, c] or None, as forward_batch_first.  In a training forward under
+        bf16 / fp16 autocast with at most 16 keys the backward is csrc/text_gate.hip on the text-side operands; the forward is
+        `unfused(visual)` (default: forward_batch_first), bit for bit, or with OCPG_TEXT_GATE_FUSED=fwd the kernel's.  Every other call
+        (no grad, fp32, more keys), and OCPG_TEXT_GATE_FUSED=0, is forward_batch_first.  `shared`: a dict of the caller's, alive for one
+        forward, in which the calls of that forward share the text-side operands."""
+        if unfused is None:
+            def unfused(v):
+                return self.forward_batch_first(v, text, text_key_padding_mask, text_pos)
+        out = text_gate_func.text_gate(self.multihead_attn, visual, text, text_key_padding_mask, text_pos, unfused, shared)
+        if out is not None:
+            return out
+        return self.forward_batch_first(visual, text, text_key_padding_mask, text_pos)
 
     def forward_batch_first(self, visual, text, text_key_padding_mask=None, text_pos=None):
         """visual [b, L, c] (the channels-last map's own memory) -> [b, L, c], or None when the attention kernel does not serve the call."""
