@@ -752,6 +752,29 @@ int ocpg_text_gate_bwd_h16(const float* x, const float* g, const void* Kp, const
                            const unsigned char* key_pad, float scale, int B, int L, int C, int H, int Lk, float* dx, float* part, void* ws,
                            int dtype, void* stream);
 
+/* Inference tail of the mask output (csrc/mask_tail.hip): the stride-4 mask logits straight to what the
+ * drivers write -- replaces, per output pixel and with no intermediate tensor, the chain of inference_davis.py:233-261 /
+ * inference_ytvos.py (and the eval branch's nearest x4, models/ocpg.py:371-372): nearest x `up`, un-pad crop, bilinear resize to
+ * the original size (align_corners=False), sigmoid, then threshold or multi-object merge.
+ *   src [K, N, hs, ws] fp32 logits (K objects, N frames).
+ *   Virtual map   V[y][x] = src[y / up][x / up] for y < crop_h, x < crop_w; 1 <= crop_h <= hs*up, 1 <= crop_w <= ws*up.
+ *   Bilinear      ATen's rule in fp32 and in ATen's operation order: scale = (float)crop / out; s = scale*(d + 0.5f) - 0.5f clamped
+ *                 at 0; i0 = (int)s; i1 = i0 + (i0 < crop-1) (against the CROP, not hs*up); l1 = s - i0; l0 = 1 - l1;
+ *                 v = l0y*(l0x*a + l1x*b) + l1y*(l0x*c + l1x*d).
+ *   Sigmoid       p = 1 / (1 + expf(-v)).
+ *   mode 0        out fp32  [N, out_h, out_w] = p.                           K must be 1.
+ *   mode 1        out uint8 [N, out_h, out_w] = p > thr ? on_value : 0.      K must be 1; 0 <= on_value <= 255.
+ *   mode 2        out uint8 [N, out_h, out_w] = label (inference_davis.py:253-261): p_k < thr becomes 0, candidates [bg, p_1 .. p_K],
+ *                 index of the FIRST maximum (ascending scan, strict >: torch.argmax's tie rule).  K <= 255.
+ * thr / bg / on_value are ignored by the modes that do not name them.  out is fully overwritten; it needs no alignment beyond its
+ * element type's (aligned 16-byte / 4-byte stores are used wherever a lane's 4 pixels allow).  One launch, no atomics, no
+ * synchronisation, sizes by value: capturable.
+ * Return codes, all before any launch: any size (K, N, hs, ws, up, crop_*, out_*) <= 0: -1006;  mode outside 0..2: -2104;
+ * K != 1 in modes 0 / 1: -2101;  K > 255 in mode 2: -2103;  crop_h > hs*up or crop_w > ws*up: -2102;  on_value outside 0..255 in
+ * mode 1: -2105;  out_h > 4*65535 or N > 65535 (grid axes): -1008;  src NULL: -1001;  out NULL: -1015. */
+int ocpg_mask_tail_f32(const float* src, int K, int N, int hs, int ws, int up, int crop_h, int crop_w, int out_h, int out_w, int mode,
+                       float thr, float bg, int on_value, void* out, void* stream);
+
 /* library / build identification: returns e.g. "ocpg_hip gfx950 r1" */
 const char* ocpg_hip_version(void);
 

@@ -2,16 +2,42 @@
 inference_davis.py:196-262, inference_ytvos.py has the same core): chop the video into clips of at most `clip_len` frames, run the
 model in eval mode on each clip, keep the query with the highest mean score over the clip, un-pad, resize the mask logits to
 the original resolution, sigmoid; `merge_objects` forms the multi-object label map.  Image loading / transforms / palette PNG
-writing stay with the caller (datasets are out of scope)."""
+writing stay with the caller (datasets are out of scope).  Opt-in native form (`native=True`, `segment_objects`): the mask head for
+the best query only and the whole tail after the model as one HIP kernel."""
 import torch
 import torch.nn.functional as F
 
+from .models.ops.functions.mask_tail_func import mask_binary, mask_labels, mask_probabilities
+
 
 @torch.no_grad()
-def segment_video(model, frames, expression, clip_len=36, origin_size=None, amp_dtype=None):
+def _selected_clips(model, frames, expression, clip_len, amp_dtype):
+    """The native clip loop: OCPG.forward_selected per clip -> (logits [T, k] of the best query, stride-4 mask logits [T, 2h, 2w],
+    their factor to the padded frame)."""
+    video_len, _, img_h, img_w = frames.shape
+    size = torch.as_tensor([int(img_h), int(img_w)], device=frames.device)
+    all_logits, all_low, up = [], [], 4
+    for start in range(0, video_len, clip_len):
+        imgs = frames[start:start + clip_len]
+        with torch.autocast(device_type=frames.device.type, dtype=amp_dtype, enabled=amp_dtype is not None):
+            outputs = model.forward_selected([imgs], [expression] if isinstance(expression, str) else expression, [{"size": size}])
+        up = outputs["mask_up"]
+        all_logits.append(outputs["pred_logits"][0, :, 0])
+        all_low.append(outputs["pred_masks_low"][0].float())
+    return torch.cat(all_logits, 0), torch.cat(all_low, 0), up
+
+
+@torch.no_grad()
+def segment_video(model, frames, expression, clip_len=36, origin_size=None, amp_dtype=None, native=False):
     """frames [T,3,H,W] (already normalised, on the model's device); expression: str or PrecomputedText.
-    Returns (logits [T,K] of the selected query, masks [T,H0,W0] in (0,1)); H0,W0 = origin_size or (H,W)."""
+    Returns (logits [T,K] of the selected query, masks [T,H0,W0] in (0,1)); H0,W0 = origin_size or (H,W).
+    native=True: the mask head runs for the best query only (OCPG.forward_selected) and the x4 / un-pad / resize / sigmoid tail is one
+    HIP kernel over the stride-4 logits (csrc/mask_tail.hip); same return contract."""
     model.eval()
+    if native:
+        logits, low, up = _selected_clips(model, frames, expression, clip_len, amp_dtype)
+        origin = tuple(origin_size) if origin_size is not None else tuple(frames.shape[-2:])
+        return logits, mask_probabilities(low, up, tuple(frames.shape[-2:]), origin)
     video_len, _, img_h, img_w = frames.shape
     out_h, out_w = origin_size if origin_size is not None else (img_h, img_w)
     size = torch.as_tensor([int(img_h), int(img_w)], device=frames.device)
@@ -33,6 +59,22 @@ def segment_video(model, frames, expression, clip_len=36, origin_size=None, amp_
     return torch.cat(all_logits, 0), torch.cat(all_masks, 0)
 
 
+@torch.no_grad()
+def segment_objects(model, frames, expressions, clip_len=36, origin_size=None, amp_dtype=None, threshold=0.3, background=0.1):
+    """The multi-object (DAVIS) driver, natively: every expression through OCPG.forward_selected, then ONE merge launch per clip
+    over the stride-4 logits [K, t, 2h, 2w] (csrc/mask_tail.hip, mode 2) -- the [K, T, H0, W0] probabilities segment_video +
+    merge_objects stack up never exist.  Returns (logits [K, T, k] of each expression's best query, labels uint8 [T, H0, W0]:
+    0 = background, i + 1 = expressions[i])."""
+    model.eval()
+    origin = tuple(origin_size) if origin_size is not None else tuple(frames.shape[-2:])
+    per = [_selected_clips(model, frames, e, clip_len, amp_dtype) for e in expressions]
+    up = per[0][2]
+    low = torch.stack([p[1] for p in per])                                         # [K, T, 2h, 2w]
+    labels = [mask_labels(low[:, s:s + clip_len], up, tuple(frames.shape[-2:]), origin, threshold, background)
+              for s in range(0, frames.shape[0], clip_len)]
+    return torch.stack([p[0] for p in per]), torch.cat(labels, 0)
+
+
 def merge_objects(masks, threshold=0.3, background=0.1):
     """masks [num_obj, T, h, w] in (0,1) -> uint8 [T, h, w]: 0 = background, i+1 = object i (inference_davis.py:253-259)."""
     masks = masks.clone()
@@ -42,10 +84,12 @@ def merge_objects(masks, threshold=0.3, background=0.1):
 
 
 def write_expression_masks(model, root, split, out_dir, videos=None, exclude_split=None, threshold=0.5, clip_len=None, device=None,
-                           amp_dtype=None, transform=None):
+                           amp_dtype=None, transform=None, native=False):
     """Ref-YouTube-VOS style inference to files (reference inference_ytvos.py:168-245): for every video of the split and every
     expression, segment the whole video (one clip unless clip_len is given), threshold the probabilities at `threshold` and write
-    <out_dir>/Annotations/<video>/<exp_id>/<frame>.png (8-bit, 0 / 255).  Returns the number of frames written."""
+    <out_dir>/Annotations/<video>/<exp_id>/<frame>.png (8-bit, 0 / 255).  Returns the number of frames written.
+    native=True: best-query mask head + the fused tail (csrc/mask_tail.hip, mode 1): the 0 / 255 bytes the PNG writer reads come
+    straight from the stride-4 logits."""
     import os
 
     from PIL import Image
@@ -62,8 +106,12 @@ def write_expression_masks(model, root, split, out_dir, videos=None, exclude_spl
         origin = tuple(raw.shape[-2:])
         frames, _ = transform(raw.to(device), None)
         for exp_id, e in data[video]["expressions"].items():
-            _, masks = segment_video(model, frames, e["exp"], clip_len=clip_len or len(names), origin_size=origin, amp_dtype=amp_dtype)
-            binary = (masks > threshold).to(torch.uint8).mul(255).cpu().numpy()
+            if native:
+                _, low, up = _selected_clips(model.eval(), frames, e["exp"], clip_len or len(names), amp_dtype)
+                binary = mask_binary(low, up, tuple(frames.shape[-2:]), origin, threshold, 255).cpu().numpy()
+            else:
+                _, masks = segment_video(model, frames, e["exp"], clip_len=clip_len or len(names), origin_size=origin, amp_dtype=amp_dtype)
+                binary = (masks > threshold).to(torch.uint8).mul(255).cpu().numpy()
             folder = os.path.join(out_dir, "Annotations", video, exp_id)
             os.makedirs(folder, exist_ok=True)
             for name, m in zip(names, binary):

@@ -17,6 +17,7 @@ MI355X-first differences in HOW (results agree to fp32 rounding):
 import copy
 import math
 import os
+from types import SimpleNamespace
 
 import torch
 import torch.nn.functional as F
@@ -238,7 +239,25 @@ class OCPG(nn.Module):
         with amp_cache.scope(self):        # one fused low-precision cast of all autocast-consumed parameters
             return self._forward(samples, captions, targets)
 
-    def _forward(self, samples, captions, targets):
+    def forward_selected(self, samples, captions, targets):
+        """Eval forward of the YTVOS / DAVIS branch that evaluates the mask head for the clip's best query only.  The best query
+        depends on pred_logits alone, so it is known before any mask exists: `forward` runs layers x queries parameter sets per
+        frame through the dynamic mask head and keeps one, this runs that one.  Returns pred_logits / pred_boxes / reference_points
+        as the eval branch does, pred_masks_low [b, t, 2h, 2w] = the MSO output at stride 4 (forward's pred_masks is its nearest x4)
+        and mask_up = 4, the factor between the two."""
+        if self.training:
+            raise RuntimeError("forward_selected is an inference path: call model.eval() first")
+        if self.args.dataset_file in ("a2d", "jhmdb") or "refcoco" in self.args.dataset_file:
+            raise RuntimeError(f"forward_selected serves the best-query (YTVOS / DAVIS) eval branch only, not {self.args.dataset_file}")
+        with amp_cache.scope(self):
+            return self._forward(samples, captions, targets, selected=True)
+
+    def _forward(self, samples, captions, targets, selected=False):
+        s = self._trunk(samples, captions, targets)
+        return self._best_query_masks(s, targets) if selected else self._all_masks(s, targets)
+
+    def _trunk(self, samples, captions, targets):
+        """Backbone, fusion, transformer, class / box heads and the mask head's operands: everything the mask evaluations share."""
         if not isinstance(samples, NestedTensor):
             samples = nested_tensor_from_videos_list(samples, 1 if self.training else 16)
         features, visual_pos = self.backbone(samples)        # NB: folds samples to [(b t), ...] in place
@@ -310,6 +329,36 @@ class OCPG(nn.Module):
         nq = self.num_queries
         params = self.controller(hs.transpose(0, 1)).reshape(b, t * nl * nq, -1)                 # hs [l, b*t, q, c]
         refs = inter_references[..., :2].transpose(0, 1).reshape(b, t * nl * nq, 2)
+        return SimpleNamespace(out=out, hs=hs, features=features, samples=samples, b=b, t=t, nl=nl, nq=nq, dev=dev, tar=tar,
+                               inter_references=inter_references, outputs_class=outputs_class, outputs_coord=outputs_coord,
+                               memory_fusion=memory_fusion, mask_features=mask_features, params=params, refs=refs,
+                               text_sentence=text_sentence)
+
+    def _best_query_masks(self, s, targets):
+        """forward_selected's mask evaluation: the best query is known from pred_logits, so only ITS parameter set of the last layer
+        goes through the mask head (t sets per clip instead of t*l*q).  The controller has run on the same rows as for `_all_masks`
+        (its cost is negligible and its GEMMs pick the same kernels), and a set's arithmetic in csrc/dynmask.hip does not depend on how
+        many sets share the launch, so from one trunk this is what the eval branch of `_all_masks` refines, bit for bit."""
+        out, b, t, nl, nq = dict(s.out), s.b, s.t, s.nl, s.nq
+        scores = out["pred_logits"].sigmoid().mean(1).max(-1)[0]               # [b, q]
+        best = scores.argmax(-1)                                                # [b]
+        bi = torch.arange(b, device=s.dev)
+        out["pred_logits"] = out["pred_logits"][bi, :, best][:, :, None]
+        out["pred_boxes"] = out["pred_boxes"][bi, :, best][:, :, None]
+        out["reference_points"] = s.inter_references[-2].unflatten(0, (b, t))[bi, :, best][:, :, None, :2]
+        p_best = s.params.view(b, t, nl, nq, -1)[:, :, -1][bi, :, best]        # [b, t, n_params]
+        r_best = s.refs.view(b, t, nl, nq, 2)[:, :, -1][bi, :, best]           # [b, t, 2]
+        m = self.dynamic_mask_with_coords(s.mask_features, p_best, r_best, targets)              # [b, t, 16, h, w]
+        pm = self.mask_refine(m.flatten(0, 1), s.features[:2])                  # [(b t), 1, 2h, 2w]
+        out["pred_masks_low"] = pm.squeeze(1).unflatten(0, (b, t))
+        out["mask_up"] = 4
+        return out
+
+    def _all_masks(self, s, targets):
+        """forward's mask evaluation: every decoder layer's every query, then the training / eval branches."""
+        out, hs, features, samples, b, t, nl, nq, dev, tar = dict(s.out), s.hs, s.features, s.samples, s.b, s.t, s.nl, s.nq, s.dev, s.tar
+        inter_references, outputs_class, outputs_coord = s.inter_references, s.outputs_class, s.outputs_coord
+        memory_fusion, mask_features, params, refs, text_sentence = s.memory_fusion, s.mask_features, s.params, s.refs, s.text_sentence
         m_all = self.dynamic_mask_with_coords(mask_features, params, refs, targets)             # [b, (t l q), 16, h, w]
         sh_all = F.pixel_shuffle(m_all.flatten(0, 1), 4).squeeze(1).view(b, t, nl, nq, 4 * tar[0], 4 * tar[1])
         m_all = m_all.view(b, t, nl, nq, 16, tar[0], tar[1])
