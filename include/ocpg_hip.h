@@ -775,6 +775,27 @@ int ocpg_text_gate_bwd_h16(const float* x, const float* g, const void* Kp, const
 int ocpg_mask_tail_f32(const float* src, int K, int N, int hs, int ws, int up, int crop_h, int crop_w, int out_h, int out_w, int mode,
                        float thr, float bg, int on_value, void* out, void* stream);
 
+/* DAVIS-2017 J&F scoring as integer counts (csrc/jf_metrics.hip; reference davis2017/metrics.py:
+ * db_eval_iou, f_measure, _seg2bmap).  The fp64 arithmetic on the counts is ocpg_amd/metrics.py:jf_from_counts.
+ *   gt, res [T, H, W] uint8 label maps: 0 = background, k = object / proposal k.  Neither pointer needs any alignment.
+ *   void_label 0..255: pixels with gt == void_label are removed from both maps, for every pair; -1: none.
+ *   Pairs         all_pairs = 0: P = G, pair p = (result id p+1, gt id p+1), R is ignored.
+ *                 all_pairs = 1: P = R*G, pair r*G + g = (result id r+1, gt id g+1).
+ *   Per pair and frame: A = (res == id_r) & ~void, B = (gt == id_g) & ~void.  Boundary map b(M) (_seg2bmap at equal size; pixels
+ *                 outside the image count as 0): y < H-1, x < W-1: (M^M[y,x+1]) | (M^M[y+1,x]) | (M^M[y+1,x+1]);  last row, x < W-1:
+ *                 M[H-1,x]^M[H-1,x+1];  last column, y < H-1: M[y,W-1]^M[y+1,W-1];  corner (H-1, W-1): 0.
+ *                 A boundary pixel of one map is matched if the other map has a boundary pixel at an in-image offset (dx, dy) with
+ *                 dx^2 + dy^2 <= radius^2 (cv2.dilate with skimage.morphology.disk(radius), default border: outside never wins).
+ *   counts [P, T, 6] int32, every element overwritten: |A&B|, |A|B|, |b(A)|, |b(B)|, matched pixels of b(A), matched pixels of b(B).
+ * Integer arithmetic only: the same result on every call.  A fill kernel zeroes counts (no memset node), one kernel adds per-tile
+ * sums with integer atomics (one per workgroup and non-zero count), sizes by value: capturable.
+ * Served: 1 <= radius <= 64, G and R <= 254, H*W < 2^31, T <= 65535 and P <= 65535 (grid axes).
+ * Return codes, all before any launch: T, H, W, G (or R with all_pairs) <= 0: -1006;  all_pairs outside 0..1: -2201;  radius
+ * outside 1..64: -2202;  G (or R with all_pairs) > 254: -2203;  void_label outside -1..255: -2204;  H*W >= 2^31: -2205;  T or P
+ * > 65535 or more than 2^31-1 tiles: -1008;  gt or res NULL: -1001;  counts NULL: -1015. */
+int ocpg_jf_counts_u8(const unsigned char* gt, const unsigned char* res, int T, int H, int W, int G, int R, int radius, int void_label,
+                      int all_pairs, int* counts, void* stream);
+
 /* library / build identification: returns e.g. "ocpg_hip gfx950 r1" */
 const char* ocpg_hip_version(void);
 

@@ -153,6 +153,7 @@ SIGNATURES = {
     "ocpg_text_gate_fwd_h16": [_vp] * 6 + [ctypes.c_float] + [_int] * 5 + [_vp, _int, _vp],
     "ocpg_text_gate_bwd_h16": [_vp] * 7 + [ctypes.c_float] + [_int] * 5 + [_vp, _vp, _vp, _int, _vp],
     "ocpg_mask_tail_f32": [_vp] + [_int] * 10 + [ctypes.c_float, ctypes.c_float, _int, _vp, _vp],
+    "ocpg_jf_counts_u8": [_vp, _vp] + [_int] * 8 + [_vp, _vp],
     "ocpg_win_attn_fwd": [_vp, _vp, _vp, ctypes.c_float] + [_int] * 5 + [_vp, _vp, _int, _vp],
     "ocpg_win_attn_bwd": [_vp, _vp, _vp, _vp, ctypes.c_float] + [_int] * 5 + [_vp] * 6 + [_int, _vp],
     "ocpg_win_attn_bwd_mfma": [_vp, _vp, _vp, _vp, ctypes.c_float] + [_int] * 5 + [_vp] * 6 + [_int, _vp],
