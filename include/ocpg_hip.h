@@ -796,6 +796,38 @@ int ocpg_mask_tail_f32(const float* src, int K, int N, int hs, int ws, int up, i
 int ocpg_jf_counts_u8(const unsigned char* gt, const unsigned char* res, int T, int H, int W, int G, int R, int radius, int void_label,
                       int all_pairs, int* counts, void* stream);
 
+/* Weak-annotation similarity head (csrc/sim_heat.hip; reference pre_process/sim_model.py:35-134).
+ *   feat [F, h*w, C] fp32, channels contiguous per pixel, 16-byte aligned.  k^_p = feat[f, p] / |feat[f, p]|_2 (an all-zero vector is
+ *   outside the contract: the reference divides by zero there).
+ *   Objects       obj_frame [n_obj] int32 (device): the frame of object o.  cand_off [n_obj + 1] int32, cand_off[0] = 0, ascending:
+ *                 object o owns candidates cand_off[o] .. cand_off[o+1]-1 of cand_xy [total, 2] int32 (device; x, y feature cells,
+ *                 0 <= x < w, 0 <= y < h), total = cand_off[n_obj].  cand_off is passed twice: cand_off_host (host memory, validated
+ *                 before any launch and used to size the grid) and cand_off (the same numbers in device memory, read by the kernels).
+ *   Per candidate c of an object, over the pixels p of the object's frame:  a_c[p] = k^_c . k^_p,
+ *                 s_c[p] = (a_c[p] - min_p a_c) / max_p a_c   (divided by the maximum, not the range, as the reference has it).
+ *   box NULL      point mode: heat[o] = s of the object's candidate 0, choice[o] = 0, score (if given) = 0.
+ *   box [n_obj, 4] int32 (device; x0, y0, x1, y1 feature cells, ends exclusive):  mx[x] = max_y s_c, my[y] = max_x s_c,
+ *                 bx[x] = (x0 <= x < x1), by[y] = (y0 <= y < y1),
+ *                 score_c = 0.5 * (sum mx*bx / (sum(mx + bx - mx*bx) + 1e-5) + sum my*by / (sum(my + by - my*by) + 1e-5)),
+ *                 choice[o] = the candidate (index within the object) of the highest score, the lowest index among equals;
+ *                 heat[o] = that candidate's s.
+ *   An object without candidates gets a zero plane and choice -1.
+ *   heat [n_obj, h, w] fp32 and choice [n_obj] int32 are fully overwritten; score [total] fp32 or NULL.
+ *   workspace: ocpg_sim_heat_workspace(F, h, w, total) bytes of device memory, 16-byte aligned (inverse norms [F, h*w], the
+ *   similarity rows [total, h*w], per-candidate min / max / score).
+ * fp32 in, fp32 accumulate, sums in a fixed order: the same result on every call.  Four launches (norms, rows, per-candidate
+ * reduction, selection), no atomics, no memset, plain vector stores only; cells and frames read from device memory are clamped into
+ * range before they address anything.
+ * Served: C % 4 == 0, h*w <= 8192, at most 256 candidates per object, n_obj <= 65535, F*h*w < 2^31.
+ * Return codes, all before any launch: feat NULL or not 16-byte aligned: -1001;  F <= 0: -1002;  h <= 0: -1003;  w <= 0 or
+ * h*w > 8192 or F*h*w >= 2^31: -1004;  C <= 0 or C % 4 != 0: -1005;  n_obj <= 0 or > 65535: -1006;  obj_frame NULL: -1007;
+ * cand_off_host NULL, cand_off_host[0] != 0, not ascending, or more than 256 candidates in one object: -1008;  cand_off NULL: -1009;
+ * cand_xy NULL with total > 0: -1010;  heat NULL: -1012;  choice NULL: -1013;  workspace NULL or not 16-byte aligned: -1015. */
+long long ocpg_sim_heat_workspace(int F, int h, int w, int total);
+int ocpg_sim_heat_f32(const float* feat, int F, int h, int w, int C, int n_obj, const int* obj_frame, const int* cand_off_host,
+                      const int* cand_off, const int* cand_xy, const int* box, float* heat, int* choice, float* score, void* workspace,
+                      void* stream);
+
 /* library / build identification: returns e.g. "ocpg_hip gfx950 r1" */
 const char* ocpg_hip_version(void);
 

@@ -154,6 +154,8 @@ SIGNATURES = {
     "ocpg_text_gate_bwd_h16": [_vp] * 7 + [ctypes.c_float] + [_int] * 5 + [_vp, _vp, _vp, _int, _vp],
     "ocpg_mask_tail_f32": [_vp] + [_int] * 10 + [ctypes.c_float, ctypes.c_float, _int, _vp, _vp],
     "ocpg_jf_counts_u8": [_vp, _vp] + [_int] * 8 + [_vp, _vp],
+    "ocpg_sim_heat_workspace": [_int] * 4,
+    "ocpg_sim_heat_f32": [_vp] + [_int] * 5 + [_vp] * 10,
     "ocpg_win_attn_fwd": [_vp, _vp, _vp, ctypes.c_float] + [_int] * 5 + [_vp, _vp, _int, _vp],
     "ocpg_win_attn_bwd": [_vp, _vp, _vp, _vp, ctypes.c_float] + [_int] * 5 + [_vp] * 6 + [_int, _vp],
     "ocpg_win_attn_bwd_mfma": [_vp, _vp, _vp, _vp, ctypes.c_float] + [_int] * 5 + [_vp] * 6 + [_int, _vp],
@@ -164,7 +166,7 @@ SIGNATURES = {
 
 # ---- optional live kernel timing (bench.py): HIP events on the launch stream around every library call ----------
 _TIMING = {"on": False, "events": []}
-_UNTIMED = ("ocpg_text_gate_rows", "ocpg_text_gate_splits", "ocpg_win_attn_dtable_supported", "ocpg_conv3x3_mfma_body_splits", "ocpg_gemm_dgrad_bn_tile", "ocpg_conv3x3_mfma_wgrad_splits", "ocpg_window_sums3x3_cl_bands", "ocpg_lfm_dft_supported", "ocpg_lfm_dft_split", "ocpg_conv3x3_mfma_splits", "ocpg_gemm_set_tuning", "ocpg_gemm_export_picks", "ocpg_gemm_import_picks", "ocpg_colsum_blocks", "ocpg_mso_wgrad_rows", "ocpg_gemm_plans", "ocpg_gemm_tuned", "ocpg_gemm_tune_rejected", "ocpg_bias_relu_dropout_bwd_slots", "ocpg_dropout_add_ln_bwd_slots", "ocpg_groupnorm_cl_work")
+_UNTIMED = ("ocpg_sim_heat_workspace", "ocpg_text_gate_rows", "ocpg_text_gate_splits", "ocpg_win_attn_dtable_supported", "ocpg_conv3x3_mfma_body_splits", "ocpg_gemm_dgrad_bn_tile", "ocpg_conv3x3_mfma_wgrad_splits", "ocpg_window_sums3x3_cl_bands", "ocpg_lfm_dft_supported", "ocpg_lfm_dft_split", "ocpg_conv3x3_mfma_splits", "ocpg_gemm_set_tuning", "ocpg_gemm_export_picks", "ocpg_gemm_import_picks", "ocpg_colsum_blocks", "ocpg_mso_wgrad_rows", "ocpg_gemm_plans", "ocpg_gemm_tuned", "ocpg_gemm_tune_rejected", "ocpg_bias_relu_dropout_bwd_slots", "ocpg_dropout_add_ln_bwd_slots", "ocpg_groupnorm_cl_work")
 
 
 def enable_kernel_timing(on=True):
@@ -266,6 +268,7 @@ def lib():
         L.ocpg_dropout_add_ln_bwd_slots.restype = ctypes.c_longlong
         L.ocpg_groupnorm_cl_work.restype = ctypes.c_longlong
         L.ocpg_colsum_blocks.restype = ctypes.c_longlong
+        L.ocpg_sim_heat_workspace.restype = ctypes.c_longlong
         _lib = _Lib(L)
     return _lib
 
