@@ -828,6 +828,31 @@ int ocpg_sim_heat_f32(const float* feat, int F, int h, int w, int C, int n_obj, 
                       const int* cand_off, const int* cand_xy, const int* box, float* heat, int* choice, float* score, void* workspace,
                       void* stream);
 
+/* A2D-Sentences / JHMDB-Sentences evaluation as integer counts (csrc/refmask_counts.hip; reference
+ * engine.py:126-194, models/postprocessors.py:14-53, datasets/a2d_eval.py).  The fp64 arithmetic on the counts is
+ * ocpg_amd/metrics.py: coco_ap_single_gt, RefMaskAccumulator.
+ *   src [B, Q, hs, ws] fp32 logits: the annotated frame of each sample, padded to the batch.
+ *   Geometry      [B, 4] int32 per sample: crop_h, crop_w (the un-padded augmented size), out_h, out_w (the original size).  Passed
+ *                 twice: geom_host (host memory, validated before any launch) and geom (the same numbers in device memory, read by
+ *                 the kernel, which clamps them into range again before they address anything).
+ *   Ground truth  gt: bytes, non-zero = set; sample b's [out_h, out_w] row-major plane starts at gt + gt_off[b] (gt_off [B] int64 in
+ *                 device memory).  No alignment is needed; planes that start on a 4-byte boundary are read 32 bits at a time on
+ *                 every row.  Nothing outside a plane's out_h * out_w bytes is read.
+ *   Per pixel     exactly ocpg_mask_tail_f32 mode 1: V[y][x] = src[b][q][y / up][x / up] for y < crop_h, x < crop_w; ATen's
+ *                 align_corners=False source index in fp32 and in ATen's operation order; the blend; p = 1 / (1 + expf(-v));
+ *                 P = p > thr, negated when invert = 1 (the reference's 1 - (sigmoid > 0.5)).
+ *   counts [B, Q, 3] int32, every element overwritten: |P & G|, |P|, |G|.
+ *   max_out_h / max_out_w: at least every sample's out_h / out_w; they size the grid.
+ * Integer arithmetic only: the same result on every call, whatever counts held before.  A fill kernel zeroes counts (no memset
+ * node), one kernel adds per-workgroup sums with integer atomics (one per workgroup and non-zero count): capturable.
+ * Return codes, all before any launch (counts untouched): B, Q, hs, ws, up, max_out_h, max_out_w or any geometry entry <= 0: -1006;
+ * invert outside 0..1: -2301;  crop_h > hs*up or crop_w > ws*up: -2302;  out_h*out_w >= 2^31: -2303;  out_h > max_out_h or
+ * out_w > max_out_w: -2304;  geom_host or geom NULL: -2305;  gt or gt_off NULL: -2306;  max_out_h > 4*65535, B*ceil(Q/64) > 65535,
+ * hs*up, ws*up or B*Q*3 >= 2^31 (grid axes and index range): -1008;  src NULL: -1001;  counts NULL: -1015. */
+int ocpg_refmask_counts_f32(const float* src, int B, int Q, int hs, int ws, int up, const int* geom_host, const int* geom,
+                            const unsigned char* gt, const long long* gt_off, int max_out_h, int max_out_w, float thr, int invert,
+                            int* counts, void* stream);
+
 /* library / build identification: returns e.g. "ocpg_hip gfx950 r1" */
 const char* ocpg_hip_version(void);
 

@@ -174,3 +174,48 @@ def evaluate_referred_masks(model, data_loader, postprocessor, device, amp_dtype
     if state is None or sum(g.numel() for g in state[0]) == 0:
         return {}
     return metrics.summarize(state)
+
+
+@torch.no_grad()
+def evaluate_a2d(model, data_loader, device, amp_dtype=None, gt=None, native=None, threshold=0.5):
+    """The whole A2D-Sentences / JHMDB-Sentences evaluation (reference engine.py:126-194) from integer counts: per batch the model's
+    forward and ONE refmask_counts call (models/ops/functions/refmask_func.py) straight from `pred_masks[:, 0]` -- every query's mask
+    against the ground truth at the original resolution as (|P & G|, |P|, |G|), with the post-processor's chain (un-pad, bilinear
+    resize, sigmoid, compare, invert) inside the kernel -- and `pred_logits` as the scores.  Nothing at the original resolution is
+    materialised, no run-length string is made.  Returns the reference's 13 numbers (metrics.RefMaskAccumulator.summary): mAP 0.5:0.95,
+    AP 0.5, AP 0.75, AP small / medium / large, P@0.5 .. P@0.9, overall_iou, mean_iou.
+
+    Targets carry `orig_size`, `size`, and the ground truth as `gt_mask` [H0, W0], as evaluate_referred_masks takes it; with `gt` (the
+    path of the reference's `*_annotations_in_coco_format.json`, or the dict metrics.load_coco_gt makes of it) the mask and its `area`
+    come from there, keyed by `image_id`.  Without an `image_id` a sample is numbered (rank, position).  native: as refmask_counts.
+    With a process group scores and counts are gathered, so every rank returns the same dict; every rank enters the collective, also
+    one whose loader was empty."""
+    from . import metrics
+    from .models.ops.functions.refmask_func import refmask_counts
+    from .util.misc import get_rank, targets_to
+    if isinstance(gt, (str, bytes)) or hasattr(gt, "__fspath__"):
+        gt = metrics.load_coco_gt(gt)
+    model.eval()
+    rank, seen, pending = get_rank(), 0, []
+    for samples, targets in data_loader:
+        ids = [t["image_id"] if "image_id" in t else (rank, seen + i) for i, t in enumerate(targets)]
+        ids = [i.item() if torch.is_tensor(i) else i for i in ids]
+        seen += len(targets)
+        crops = [[int(v) for v in t["size"].tolist()] for t in targets]               # read on the host, before the targets move
+        sizes = [[int(v) for v in t["orig_size"].tolist()] for t in targets]
+        samples = samples.to(device)
+        captions = [t["caption"] for t in targets]
+        targets = targets_to(targets, device)
+        with torch.autocast(device_type=torch.device(device).type, dtype=amp_dtype, enabled=amp_dtype is not None):
+            outputs = model(samples, captions, targets)
+        if gt is not None:
+            masks, areas = [gt[i][0] for i in ids], [gt[i][1] for i in ids]
+        else:
+            masks, areas = [t["gt_mask"] for t in targets], None
+        masks = [m if m.dtype in (torch.bool, torch.uint8) else m != 0 for m in masks]
+        counts = refmask_counts(outputs["pred_masks"][:, 0].float(), 1, crops, sizes, masks, threshold=threshold, invert=True, native=native)
+        pending.append((ids, outputs["pred_logits"][:, 0, :, 0].float().sigmoid(), counts, areas))
+    acc = metrics.RefMaskAccumulator()
+    for ids, scores, counts, areas in pending:                                            # the readbacks, after the last launch
+        acc.add(ids, scores, counts, areas)
+    return acc.gather().summary()

@@ -1,7 +1,8 @@
 """Referring-segmentation metrics of the A2D-Sentences / JHMDB-Sentences evaluation (reference datasets/a2d_eval.py:29-67, fed by
 engine.py:158-189): mask IoU, precision@K, overall IoU, mean IoU -- as one batched tensor program on whatever device the masks are on
 (the reference decodes COCO RLE annotations one instance at a time on the host; the COCO-style AP numbers it also prints need
-pycocotools and are not reproduced here)."""
+pycocotools and are not reproduced here).  The same evaluation from integer counts, with the AP numbers restated from COCOeval's
+algorithm, is further down: coco_ap_single_gt, RefMaskAccumulator, load_coco_gt."""
 import math
 import warnings
 from typing import Dict, Sequence
@@ -169,3 +170,167 @@ class DavisAccumulator:
             g = {f"{k}-{name}": float(np.mean(self.stats[k][s])) for k in "JF" for s, name in zip("MRD", ("Mean", "Recall", "Decay"))}
         g["J&F-Mean"] = (g["J-Mean"] + g["F-Mean"]) / 2.0
         return {k: g[k] for k in GLOBAL_MEASURES}, dict(self.per_object)
+
+
+# ---- A2D-Sentences / JHMDB-Sentences from counts (reference engine.py:158-189, datasets/a2d_eval.py, pycocotools' COCOeval) -------------
+# Every figure of this evaluation is a function of three integers per (sample, query) -- |P & G|, |P|, |G|
+# (models/ops/functions/refmask_func.py: one HIP kernel per batch on the GPU) -- and the query's score: the task has one ground-truth
+# mask per image, no crowd regions, and categories are ignored.  Everything below is host arithmetic on those integers.
+
+AP_LABELS = ("mAP 0.5:0.95", "AP 0.5", "AP 0.75", "AP 0.5:0.95 S", "AP 0.5:0.95 M", "AP 0.5:0.95 L")
+COCO_IOU_THRESHOLDS = np.linspace(0.5, 0.95, 10)
+COCO_RECALL_THRESHOLDS = np.linspace(0.0, 1.0, 101)
+COCO_MAX_DETS = 100
+COCO_AREA_RANGES = ((0.0, 1e10), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e10))      # all, small, medium, large
+
+
+def _np(x, dtype):
+    return (x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)).astype(dtype)
+
+
+def coco_ap_single_gt(scores, counts, gt_area=None, order=None) -> Dict[str, float]:
+    """scores [N, Q], counts [N, Q, 3] = (|P & G|, |P|, |G|) per image and detection -> the reference's six AP figures (AP_LABELS).
+
+    Restates pycocotools' COCOeval (evaluate + accumulate + summarize) with iouType='segm', useCats=0 for ONE non-crowd ground truth
+    per image, in fp64 numpy, vectorised over images, detections and IoU thresholds: IoU = I / (|P| + |G| - I) and 0 where the union
+    is 0; thresholds linspace(.5, .95, 10); recall points linspace(0, 1, 101); maxDets 100; area ranges all / small / medium / large.
+    Per image and range the ground truth is ignored when gt_area (default |G|; the reference's JSON carries an `area` field) lies
+    outside the range; detections go by descending score (stable: ties keep query order); the first whose IoU reaches
+    min(t, 1 - 1e-10) takes the ground truth and inherits its ignore flag; an unmatched detection whose own area |P| lies outside
+    the range is ignored.  All detections are then merged by a stable descending sort on score -- images in `order` (a permutation of
+    range(N): ascending image_id; default insertion order) -- ignored ones are dropped, cumulative TP / FP give recall = TP / (ground
+    truths not ignored) and precision = TP / (TP + FP + spacing(1)), precision is made non-increasing from the right and sampled at
+    the first index with recall >= r for each recall point (0 past the end).  AP = mean over thresholds and recall points, -1 where a
+    range has no ground truth that is not ignored.
+    Not reproduced: COCOeval tests `dtm == 0` for "unmatched", which confuses a ground truth whose annotation id is 0 with no match;
+    here a match is a match whatever the id."""
+    s = _np(scores, np.float64)
+    c = _np(counts, np.int64)
+    if s.ndim != 2 or c.shape != s.shape + (3,):
+        raise ValueError(f"coco_ap_single_gt: expected scores [N, Q] and counts [N, Q, 3], got {s.shape} and {c.shape}")
+    n = s.shape[0]
+    if order is not None:
+        order = np.asarray(order, dtype=np.int64)
+        s, c = s[order], c[order]
+    area = c[:, 0, 2].astype(np.float64) if gt_area is None else _np(gt_area, np.float64)[order if order is not None else slice(None)]
+    if n == 0:
+        return {k: -1.0 for k in AP_LABELS}
+    rank = np.argsort(-s, axis=1, kind="stable")[:, :COCO_MAX_DETS]
+    s = np.take_along_axis(s, rank, 1)
+    inter = np.take_along_axis(c[..., 0], rank, 1).astype(np.float64)
+    det_area = np.take_along_axis(c[..., 1], rank, 1).astype(np.float64)
+    union = det_area + c[:, :1, 2] - inter
+    iou = np.where(union > 0, inter / np.where(union > 0, union, 1.0), 0.0)
+    thr = np.minimum(COCO_IOU_THRESHOLDS, 1 - 1e-10)
+    reach = iou[None] >= thr[:, None, None]                                      # [T, N, D]
+    match = reach & (np.cumsum(reach, axis=2) == 1)                              # the first that reaches it takes the one ground truth
+    flat_order = np.argsort(-s.reshape(-1), kind="stable")                       # merged over images
+    match_f = match.reshape(len(thr), -1)[:, flat_order]
+    ap = np.full((len(COCO_AREA_RANGES), len(thr)), -1.0)
+    for a, (lo, hi) in enumerate(COCO_AREA_RANGES):
+        gt_ignored = (area < lo) | (area > hi)                                   # [N]
+        n_gt = int((~gt_ignored).sum())
+        if n_gt == 0:
+            continue
+        det_out = (det_area < lo) | (det_area > hi)                              # [N, D]
+        ignored = np.where(match, gt_ignored[None, :, None], det_out[None])      # [T, N, D]
+        ignored_f = ignored.reshape(len(thr), -1)[:, flat_order]
+        for t in range(len(thr)):
+            tp = match_f[t][~ignored_f[t]]
+            ctp = np.cumsum(tp, dtype=np.float64)
+            cfp = np.cumsum(~tp, dtype=np.float64)
+            recall = ctp / n_gt
+            precision = ctp / (ctp + cfp + np.spacing(1))
+            precision = np.maximum.accumulate(precision[::-1])[::-1]
+            at = np.searchsorted(recall, COCO_RECALL_THRESHOLDS, side="left")
+            ap[a, t] = np.append(precision, 0.0)[at].mean()                       # at == len(precision): past the end, 0
+
+    def mean(x):
+        x = x[x > -1]
+        return float(x.mean()) if x.size else -1.0
+    t50, t75 = int(np.argmin(np.abs(COCO_IOU_THRESHOLDS - 0.5))), int(np.argmin(np.abs(COCO_IOU_THRESHOLDS - 0.75)))
+    values = (mean(ap[0]), mean(ap[0, t50:t50 + 1]), mean(ap[0, t75:t75 + 1]), mean(ap[1]), mean(ap[2]), mean(ap[3]))
+    return dict(zip(AP_LABELS, values))
+
+
+class RefMaskAccumulator:
+    """Collects scores and counts of the A2D / JHMDB evaluation: add(...) per batch, gather() with a process group, summary() once.
+
+    summary() returns the 13 keys of reference engine.py:183-189: the six AP figures (coco_ap_single_gt, images in ascending image_id
+    order as COCOeval sorts them) and P@0.5 .. P@0.9, overall_iou, mean_iou of the highest-scoring query per image (on equal scores
+    the last one, as select_best_query), with the per-instance IoU (I + 1e-6) / (U + 1e-6) in fp32 as mask_iou, their mean in fp64 and
+    the overall sums in int64 -- exact, as the reference's Python floats are.  An image_id added more than once (a sampler that pads
+    the last batch) counts once, the first time."""
+
+    def __init__(self):
+        self.image_ids, self.scores, self.counts, self.areas = [], [], [], []
+
+    def add(self, image_ids, scores, counts, gt_area=None):
+        """image_ids: B hashable, sortable ids; scores [B, Q]; counts [B, Q, 3]; gt_area: B numbers or None (|G|)."""
+        s, c = _np(scores, np.float32), _np(counts, np.int64)
+        if s.ndim != 2 or c.shape != s.shape + (3,) or len(image_ids) != s.shape[0]:
+            raise ValueError(f"RefMaskAccumulator.add: expected B ids, scores [B, Q], counts [B, Q, 3]; got {len(image_ids)}, {s.shape}, {c.shape}")
+        area = c[:, 0, 2].astype(np.float64) if gt_area is None else _np(gt_area, np.float64).reshape(-1)
+        for i, image_id in enumerate(image_ids):
+            self.image_ids.append(image_id.item() if torch.is_tensor(image_id) else image_id)
+            self.scores.append(s[i])
+            self.counts.append(c[i])
+            self.areas.append(float(area[i]))
+
+    def gather(self):
+        """With a process group: every rank ends with all ranks' samples, in rank order (a few bytes per sample; the reference gathers
+        every run-length string).  Every rank must call it, also one that added nothing."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+            return self
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, (self.image_ids, self.scores, self.counts, self.areas))
+        self.image_ids, self.scores, self.counts, self.areas = ([x for p in parts for x in p[k]] for k in range(4))
+        return self
+
+    def summary(self, thresholds: Sequence[float] = THRESHOLDS) -> Dict[str, float]:
+        seen, keep = set(), []
+        for i, image_id in enumerate(self.image_ids):
+            if image_id not in seen:
+                seen.add(image_id)
+                keep.append(i)
+        if not keep:
+            return {}
+        if len({len(self.scores[i]) for i in keep}) != 1:
+            raise ValueError("RefMaskAccumulator: the number of queries changed between batches")
+        scores = np.stack([self.scores[i] for i in keep])
+        counts = np.stack([self.counts[i] for i in keep])
+        areas = np.asarray([self.areas[i] for i in keep])
+        ids = [self.image_ids[i] for i in keep]
+        out = coco_ap_single_gt(scores, counts, areas, order=sorted(range(len(ids)), key=lambda i: ids[i]))
+        q = scores.shape[1]
+        best = q - 1 - np.argmax(scores[:, ::-1], axis=1)
+        c = counts[np.arange(len(ids)), best]
+        inter, union = c[:, 0], c[:, 1] + c[:, 2] - c[:, 0]
+        eps = np.float32(1e-6)
+        ious = (inter.astype(np.float32) + eps) / (union.astype(np.float32) + eps)
+        out.update({"P@%s" % k: float((ious > np.float32(k)).mean()) for k in thresholds})
+        total_union = int(union.sum())
+        out["overall_iou"] = int(inter.sum()) / total_union if total_union > 0 else 0.0
+        out["mean_iou"] = float(ious.astype(np.float64).mean())
+        return out
+
+
+def load_coco_gt(path) -> Dict:
+    """The reference's `*_annotations_in_coco_format.json` (engine.py:171-174) -> {image_id: (mask uint8 tensor [H0, W0], area)}: one
+    annotation per image, its `segmentation` a COCO run-length encoding read by models/postprocessors.py:rle_decode; `area` is the
+    JSON's field, or the mask's own where it is missing."""
+    import json
+
+    from .models.postprocessors import rle_decode
+    with open(path) as f:
+        data = json.load(f)
+    out = {}
+    for ann in data["annotations"]:
+        if ann["image_id"] in out:
+            raise ValueError(f"load_coco_gt: more than one annotation for image {ann['image_id']!r}")
+        if ann.get("iscrowd", 0):
+            raise ValueError(f"load_coco_gt: crowd annotation on image {ann['image_id']!r}")
+        mask = rle_decode(ann["segmentation"])
+        out[ann["image_id"]] = (torch.from_numpy(mask), float(ann["area"]) if "area" in ann else float(mask.sum()))
+    return out
