@@ -419,7 +419,8 @@ int ocpg_gemm_bn_act(const void* A, const void* W, void* D, const float* scale, 
  * models/segmentation.py:203-211,253-315 as called from models/criterion.py:141-178).
  *
  * Level-set loss: x [Lr,N,h,w] logits, feats [N,CF,h,w] (first C channels used, C <= 16), box [N,h,w] in {0,1}.
- *   fwd: sums [Lr,N,ceil(h*w/1024),7+2C] scratch (per-workgroup partials), coef [Lr,N,8+2C] kept for the backward; loss [Lr].
+ *   fwd: sums [Lr,N,ceil(h*w/1024),7+2C] scratch (per-workgroup partials), coef [Lr,N,8+2C] kept for the backward; loss [Lr], the
+ *        N per-frame terms added in ascending n (no atomics: the same bits on every call).
  *   bwd: gloss [Lr] upstream gradient -> gx [Lr,N,h,w], gfeat [N,CF,h,w] (may be NULL), both fully written. */
 int ocpg_levelset_fwd_f32(const float* x, const float* feats, const float* box, int Lr, int N, int C, int CF, int h, int w, float* sums,
                           float* coef, float* loss, void* stream);
@@ -852,6 +853,37 @@ int ocpg_sim_heat_f32(const float* feat, int F, int h, int w, int C, int n_obj, 
 int ocpg_refmask_counts_f32(const float* src, int B, int Q, int hs, int ws, int up, const int* geom_host, const int* geom,
                             const unsigned char* gt, const long long* gt_off, int max_out_h, int max_out_w, float thr, int invert,
                             int* counts, void* stream);
+
+/* Everything the matcher and the criterion derive from the batch's targets alone (csrc/target_pack.hip; the
+ * torch composition it stands for: models/ops/functions/target_pack_func.py).  B clips of T frames; fp32 unless noted.
+ *   Per clip i    masks[i], heat[i], weak[i]: device pointers to dense [T, H_i, W_i] maps (clips may differ in H and W), boxes[i] [T, 4]
+ *                 cxcywh, valid[i] [T] int64, labels[i] [T] int64 (labels NULL: no labels), size[i] [2] int64 (h, w).  masks .. size are
+ *                 HOST arrays of B device pointers, hw a HOST array [B, 2] of H_i, W_i: the kernels receive them by value, 16 clips per
+ *                 launch (no pointer table in device memory, no copy: capturable).
+ *   PH, PW        the padded extent (>= every H_i, W_i); pixels past a clip's own extent are zero.  sub(x, k) = x[k/2::k, k/2::k] of the
+ *                 padded map.  s, sl: the criterion's strides, sm: the matcher's, (lh, lw): the level-set map size.
+ *   gt_s [B,T,PH/s,PW/s] = sub(masks, s);  gt_m [B,T,PH/sm,PW/sm] = sub(masks, sm).
+ *   region        the box of frame t on the padded [PH, PW] grid, 1 inside: xyxy = cx -+ 0.5 * w (one rounding), scaled by size
+ *                 (w, h, w, h), truncated toward zero; bounds as the Python slice y0:y1, x0:x1 (a negative bound wraps once, then
+ *                 clamps to the axis); all zero when the truncated box has no positive width or height.
+ *                 region_s [B,T,PH/s,PW/s] = sub(region, s), region_l = sub(region, sl),
+ *                 region_ls [B*T, lh, lw] = region_s at rows min(floorf(y * ((float)(PH/s) / lh)), PH/s - 1), columns alike (nearest).
+ *   weak_s = sub(weak, s) * region_s, weak_l = sub(weak, sl) * region_l.
+ *   w_s, w_l      a = |clamp(sub(heat, k), 0.3, 0.7) - 0.5|, lo / hi = min / max of a over the whole [B,T,..] map,
+ *                 (a - lo) / (hi - lo + 1e-5) (IEEE division), 1 where the region is 0.
+ *   tboxes [B,T,4] = boxes, valid_f [B,T] fp32 and valid_i [B,T] int64 = valid, labels_out [B,T] int64 = labels.
+ *   workspace     ocpg_target_pack_workspace(B) bytes of device memory (per-workgroup min / max).
+ * Every output element is written (no pre-zeroing).  ceil(B/16) + 1 launches, no atomics, no memset, the same bits on every call.
+ * Served (else -2000, before any launch): PH % k == 0 and PW % (4 * k) == 0 for k = s, sl, sm;  lw % 4 == 0;  T*PH*PW < 2^31.
+ * Return codes, all before any launch: B <= 0: -1001;  T <= 0: -1002;  a pointer array or one of its entries NULL: -1003;  H_i or W_i
+ * <= 0 or beyond PH / PW: -1004;  PH or PW <= 0: -1005;  a stride <= 0: -1006;  lh or lw <= 0: -1007;  gt_s .. w_l or tboxes NULL or
+ * not 16-byte aligned: -1008;  valid_f, valid_i or (with labels) labels_out NULL: -1009;  workspace NULL: -1010. */
+long long ocpg_target_pack_workspace(int B);
+int ocpg_target_pack_f32(int B, int T, const void* const* masks, const void* const* heat, const void* const* weak, const int* hw,
+                         const void* const* boxes, const void* const* valid, const void* const* labels, const void* const* size, int PH,
+                         int PW, int s, int sl, int sm, int lh, int lw, float* gt_s, float* gt_m, float* region_s, float* region_l,
+                         float* region_ls, float* weak_s, float* weak_l, float* w_s, float* w_l, float* tboxes, float* valid_f,
+                         long long* valid_i, long long* labels_out, void* workspace, void* stream);
 
 /* library / build identification: returns e.g. "ocpg_hip gfx950 r1" */
 const char* ocpg_hip_version(void);

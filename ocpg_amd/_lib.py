@@ -157,6 +157,8 @@ SIGNATURES = {
     "ocpg_refmask_counts_f32": [_vp] + [_int] * 5 + [_vp] * 4 + [_int, _int, ctypes.c_float, _int, _vp, _vp],
     "ocpg_sim_heat_workspace": [_int] * 4,
     "ocpg_sim_heat_f32": [_vp] + [_int] * 5 + [_vp] * 10,
+    "ocpg_target_pack_workspace": [_int],
+    "ocpg_target_pack_f32": [_int, _int] + [_vp] * 8 + [_int] * 7 + [_vp] * 15,
     "ocpg_win_attn_fwd": [_vp, _vp, _vp, ctypes.c_float] + [_int] * 5 + [_vp, _vp, _int, _vp],
     "ocpg_win_attn_bwd": [_vp, _vp, _vp, _vp, ctypes.c_float] + [_int] * 5 + [_vp] * 6 + [_int, _vp],
     "ocpg_win_attn_bwd_mfma": [_vp, _vp, _vp, _vp, ctypes.c_float] + [_int] * 5 + [_vp] * 6 + [_int, _vp],
@@ -270,6 +272,7 @@ def lib():
         L.ocpg_groupnorm_cl_work.restype = ctypes.c_longlong
         L.ocpg_colsum_blocks.restype = ctypes.c_longlong
         L.ocpg_sim_heat_workspace.restype = ctypes.c_longlong
+        L.ocpg_target_pack_workspace.restype = ctypes.c_longlong
         _lib = _Lib(L)
     return _lib
 

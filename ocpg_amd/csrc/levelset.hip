@@ -2,7 +2,7 @@
 //
 // Reference: levelset_loss + region_levelset + length_regularization (models/segmentation.py:279-315), called from
 // SetCriterion.loss_masks (models/criterion.py:160-178) once per decoder layer and resolution: ~60 elementwise /
-// reduction kernels forward and ~120 backward per call, 8 calls per step.  Here: 2 launches forward, 1 backward.
+// reduction kernels forward and ~120 backward per call, 8 calls per step.  Here: 3 launches forward, 1 backward.
 //
 //   x     [Lr, N, h, w]   mask logits (Lr decoder layers, N = clips x frames)
 //   feats [N, CF, h, w]   level-set features, the first C (<= CF) channels are used (the criterion drops the last one)
@@ -20,13 +20,14 @@
 //   dx = (dfg - dbg) p (1 - p) box;   dfeats_c = box sum_l dt_c
 //
 // levelset_sums: one lane per pixel, 2C+7 partial sums per (layer, frame) reduced wave -> block -> one plain store per sum into
-// the workgroup's partial row; levelset_final reduces the rows (240 workgroups adding into the same 29 addresses serialise).
+// the workgroup's partial row; levelset_final reduces the rows (240 workgroups adding into the same 29 addresses serialise) and leaves
+// the frame's term in its first row; levelset_total adds the N terms of a layer in ascending n.  No atomics: the same bits on every call
+// (N atomic adds into loss[l] landed in completion order, and two runs of one step differed in the last bit).
 // HBM-bound streaming passes: (Lr + C + 1) floats in per pixel forward; backward the same in, (Lr + CF) out.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/ocpg_hip.h"
-#include "fill.h"
 
 namespace {
 
@@ -114,12 +115,11 @@ __global__ __launch_bounds__(256) void levelset_sums(const float* __restrict__ x
 
 // coef layout per (l, n): [0] k1_fg [1] k2_fg [2] k1_bg [3] k2_bg [4] (2-r)_fg [5] (2-r)_bg [6] 1/(C pixels) [7] 1e-5/pixels
 //                         [8..8+C) c_fg [8+C..8+2C) c_bg
-__global__ __launch_bounds__(64) void levelset_final(const float* __restrict__ part, int nblk, int N, int C, float* __restrict__ coef,
-                                                     float* __restrict__ loss) {
+__global__ __launch_bounds__(64) void levelset_final(float* __restrict__ part, int nblk, int N, int C, float* __restrict__ coef) {
   __shared__ float s[7 + 2 * CMAX];
   const int n = blockIdx.x, l = blockIdx.y;
   const int NS = 7 + 2 * C, NC = 8 + 2 * C;
-  const float* p = part + ((long long)l * N + n) * nblk * NS;
+  float* p = part + ((long long)l * N + n) * nblk * NS;
   for (int slot = 0; slot < NS; ++slot) {            // reduce the workgroup partials of this (layer, frame)
     float v = 0.f;
     for (int b = threadIdx.x; b < nblk; b += 64) v += p[(long long)b * NS + slot];
@@ -151,7 +151,23 @@ __global__ __launch_bounds__(64) void levelset_final(const float* __restrict__ p
   }
   k[6] = 1.f / ((float)C * pixels);
   k[7] = 0.00001f / pixels;
-  atomicAdd(loss + l, (e_tot / (float)C / pixels + 0.00001f * (s[4] + s[5]) / pixels) / (float)N);      // N adds per address
+  // this frame's term, over the first slot of its own partials (all read above, by this workgroup alone)
+  p[0] = (e_tot / (float)C / pixels + 0.00001f * (s[4] + s[5]) / pixels) / (float)N;
+}
+
+// loss[l] = the N terms levelset_final left (stride floats apart), added in ascending n
+__global__ __launch_bounds__(64) void levelset_total(const float* __restrict__ part, long long stride, int N, float* __restrict__ loss) {
+  __shared__ float t[64];
+  const float* p = part + (long long)blockIdx.x * N * stride;
+  float s = 0.f;
+  for (int n0 = 0; n0 < N; n0 += 64) {
+    __syncthreads();
+    if (n0 + (int)threadIdx.x < N) t[threadIdx.x] = p[(n0 + threadIdx.x) * stride];
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int i = 0; i < 64 && n0 + i < N; ++i) s += t[i];
+  }
+  if (threadIdx.x == 0) loss[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(256) void levelset_bwd(const float* __restrict__ x, const float* __restrict__ feats,
@@ -229,11 +245,10 @@ int ocpg_levelset_fwd_f32(const float* x, const float* feats, const float* box, 
   hipStream_t st = (hipStream_t)stream;
   const int hw = h * w;
   const int nblk = (hw + 256 * PPT - 1) / (256 * PPT);
-  hipError_t e = ocpg_fill::zero_async(loss, sizeof(float) * (size_t)Lr, st);
-  if (e != hipSuccess) return -(int)e;
   levelset_sums<<<dim3(nblk, N, Lr), 256, 0, st>>>(x, feats, box, N, C, CF, h, w, sums);
-  levelset_final<<<dim3(N, Lr), 64, 0, st>>>(sums, nblk, N, C, coef, loss);
-  e = hipGetLastError();
+  levelset_final<<<dim3(N, Lr), 64, 0, st>>>(sums, nblk, N, C, coef);
+  levelset_total<<<Lr, 64, 0, st>>>(sums, (long long)nblk * (7 + 2 * C), N, loss);
+  const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : -(int)e;
 }
 

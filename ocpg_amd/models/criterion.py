@@ -18,21 +18,14 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..util import box_ops
-from ..util.misc import get_world_size, is_dist_avail_and_initialized, nested_tensor_from_tensor_list
+from ..util.misc import get_world_size, is_dist_avail_and_initialized
 from .matcher import _assert_well_formed, _pairwise_giou_1
 from .ops.functions import mask_loss_func
-from .segmentation import generate_box_region_mask
+from .ops.functions.target_pack_func import build_target_pack
 
 HIP_MASK_LOSSES = True      # A/B switch: fused HIP level-set / projection losses on the GPU
 HIP_DET_LOSSES = True       # A/B switch: fused HIP classification / L1 / GIoU losses on the GPU
-
-
-def _pad_stack(targets, key):
-    return nested_tensor_from_tensor_list([t[key] for t in targets], size_divisibility=32, split=False).decompose()[0]
-
-
-def _sub(x, k):
-    return x[..., k // 2::k, k // 2::k]
+MASK_OUT_STRIDE, MASK_OUT_STRIDE_LOW = 1, 2     # the full- and low-resolution mask losses' sub-sampling of the /32-padded targets
 
 
 def _dice(x, t):
@@ -55,8 +48,8 @@ class SetCriterion(nn.Module):
         empty_weight[-1] = self.eos_coef
         self.register_buffer("empty_weight", empty_weight)
         self.focal_alpha = focal_alpha
-        self.mask_out_stride = 1
-        self.mask_out_stride_low = 2
+        self.mask_out_stride = MASK_OUT_STRIDE
+        self.mask_out_stride_low = MASK_OUT_STRIDE_LOW
         self.iter = 0
         self._warmup_iters = 100000
         # optional device-resident copy of `iter` (0-dim float tensor) for callers that replay a captured HIP graph: a
@@ -96,33 +89,28 @@ class SetCriterion(nn.Module):
         giou = (1 - _pairwise_giou_1(sx, tx)).sum((1, 2)) / num_boxes
         return l1, giou
 
-    def _masks_stacked(self, pm, pml, src_lst, targets, num_boxes, warm):
+    def _pack(self, targets, ls_hw, pack=None):
+        """The target pack of `targets` at this criterion's strides: the caller's, if it was built from the very same list with the same
+        strides and level-set size, else one of its own (the matcher's stride only matters to the matcher)."""
+        s, sl = self.mask_out_stride, self.mask_out_stride_low
+        ls_hw = (int(ls_hw[0]), int(ls_hw[1]))
+        if pack is not None and pack.targets is targets and pack.key[:2] == (s, sl) and pack.key[3] == ls_hw:
+            return pack
+        return build_target_pack(targets, s, sl, self.matcher.mask_out_stride if self.matcher is not None else 2, ls_hw)
+
+    def _masks_stacked(self, pm, pml, src_lst, targets, num_boxes, warm, pack=None):
         """pm [Lr,B,T,H,W] full-res logits, pml [Lr,B,T,h,w] low-res, src_lst [B,T,C,h,w], warm [Lr] (criterion.py:109-190).
         Always evaluated in fp32 (the reference's losses are elementwise/reduction ops that autocast leaves in fp32)."""
         with torch.autocast(device_type=pm.device.type, enabled=False):
-            return self._masks_stacked_fp32(pm.float(), pml.float(), src_lst.float(), targets, num_boxes, warm)
+            return self._masks_stacked_fp32(pm.float(), pml.float(), src_lst.float(), targets, num_boxes, warm, pack)
 
-    def _masks_stacked_fp32(self, pm, pml, src_lst, targets, num_boxes, warm):
+    def _masks_stacked_fp32(self, pm, pml, src_lst, targets, num_boxes, warm, pack=None):
         lr = pm.shape[0]
-        gt = _pad_stack(targets, "masks").to(pml)
-        heat = _pad_stack(targets, "weights").to(pml)
-        weak = _pad_stack(targets, "weak_masks").to(pml)
-        s, sl = self.mask_out_stride, self.mask_out_stride_low
-        im_h, im_w = gt.shape[-2:]
-        b, nf = weak.shape[:2]
-        gt_full = _sub(gt, s)
-        assert gt_full.size(2) * s == im_h and gt_full.size(3) * s == im_w
-        sizes = torch.stack([t["size"] for t in targets]).repeat_interleave(nf, dim=0)
-        boxes = box_ops.box_cxcywh_to_xyxy(torch.cat([t["boxes"] for t in targets], dim=0))
-        region = generate_box_region_mask(boxes, (im_h, im_w), sizes).view(b, nf, im_h, im_w)
-        region_low, region = _sub(region, sl), _sub(region, s)
-        weak_full, weak_low = _sub(weak, s) * region, _sub(weak, sl) * region_low
-
-        def heat_weight(h, reg):        # masked_ce_loss's weight map (segmentation.py:177-190): targets only
-            w = (h.clamp(min=0.3, max=0.7) - 0.5).abs()
-            lo, hi = w.min(), w.max()
-            w = (w - lo) / (hi - lo + 1e-5)
-            return torch.where(reg == 0, torch.ones_like(w), w)
+        lst_hw = src_lst.shape[-2:]
+        pack = self._pack(targets, lst_hw, pack)    # everything that depends on the targets alone (ops/functions/target_pack_func.py)
+        gt_full, region, region_low, region_scaled = pack.gt_s, pack.region_s, pack.region_l, pack.region_ls
+        weak_full, weak_low, w_full, w_low = pack.weak_s, pack.weak_l, pack.w_s, pack.w_l
+        b, nf = weak_full.shape[:2]
 
         def masked_ce(x, w, m):         # BCE-with-logits applied to sigmoid(x)*w (the reference's double squashing)
             return F.binary_cross_entropy_with_logits(x.sigmoid() * w, (m * w).expand_as(x), reduction="none").mean((1, 2, 3, 4))
@@ -152,14 +140,11 @@ class SetCriterion(nn.Module):
                 return (v[..., 1:, :] - v[..., :-1, :]).abs().sum((2, 3)) + (v[..., :, 1:] - v[..., :, :-1]).abs().sum((2, 3))
             return (region_e / pixels + 0.00001 * (length(fg) + length(bg)) / pixels).mean(1)
 
-        w_full, w_low = heat_weight(_sub(heat, s), region), heat_weight(_sub(heat, sl), region_low)
         if pm.is_cuda and HIP_MASK_LOSSES and pm[0].numel() % 4 == 0 and pml[0].numel() % 4 == 0:
             loss_mask, loss_mask_low = mask_loss_func.masked_ce(pm, w_full, weak_full), mask_loss_func.masked_ce(pml, w_low, weak_low)
         else:
             loss_mask, loss_mask_low = masked_ce(pm, w_full, weak_full), masked_ce(pml, w_low, weak_low)
-        lst_hw = src_lst.shape[-2:]
         scaled = F.interpolate(pm.flatten(0, 1), lst_hw, mode="bilinear", align_corners=True).view(lr, b * nf, *lst_hw)
-        region_scaled = F.interpolate(region, lst_hw, mode="nearest").flatten(0, 1)
         feats = src_lst.flatten(0, 1)[:, :-1]
         if pm.is_cuda and HIP_MASK_LOSSES and feats.shape[1] <= 16:
             # fused HIP kernels (csrc/levelset.hip, csrc/proj.hip): 2-3 launches per loss instead of ~30-60 (+ twice that backward)
@@ -241,6 +226,11 @@ class SetCriterion(nn.Module):
 
         losses, maps = {}, (None, None, None)
         per_layer = {}
+        pack = outputs.get("_target_pack")         # the model built it before matching: valid only for the very list it was built from
+        if pack is not None and pack.targets is not targets:
+            pack = None
+        if "masks" in self.losses:
+            pack = self._pack(targets, outputs["ls_features"].shape[-2:], pack)
         if HIP_DET_LOSSES and "labels" in self.losses and "boxes" in self.losses and src.is_cuda:
             # one launch (csrc/det_loss.hip) instead of ~70 tiny kernels forward and ~140 backward
             from .matcher import _BOX_ERRORS
@@ -248,10 +238,13 @@ class SetCriterion(nn.Module):
             flag = _BOX_ERRORS.get(dev)
             if flag is None and not torch.cuda.is_current_stream_capturing():
                 flag = _BOX_ERRORS[dev] = torch.zeros((), dtype=torch.int32, device=dev)
-            valid = torch.stack([t["valid"] for t in targets]).to(dev)
-            labels = None if self.num_classes == 1 else torch.stack([t["labels"] for t in targets]).to(dev)
-            tboxes = torch.stack([t["boxes"] for t in targets]).to(dev)
-            det = mask_loss_func.det_losses(stacked("pred_logits"), stacked("pred_boxes"), src, valid, labels, tboxes, num_boxes,
+            if pack is not None:
+                valid, labels, tboxes = pack.valid_f, None if self.num_classes == 1 else pack.labels, pack.tboxes
+            else:
+                valid = torch.stack([t["valid"] for t in targets]).to(dev)
+                labels = None if self.num_classes == 1 else torch.stack([t["labels"] for t in targets]).to(dev)
+                tboxes = torch.stack([t["boxes"] for t in targets]).to(dev)
+            det =mask_loss_func.det_losses(stacked("pred_logits"), stacked("pred_boxes"), src, valid, labels, tboxes, num_boxes,
                                             self.focal_alpha, flag)
             per_layer["loss_ce"], per_layer["loss_bbox"], per_layer["loss_giou"] = det.unbind(0)
         else:
@@ -261,7 +254,7 @@ class SetCriterion(nn.Module):
                 per_layer["loss_bbox"], per_layer["loss_giou"] = self._boxes_stacked(stacked("pred_boxes"), src, targets, num_boxes)
         if "masks" in self.losses:
             warm = self._warm(len(layers)).to(outputs["pred_masks_low"].device)
-            d, maps = self._masks_stacked(stacked("pred_masks"), stacked("pred_masks_low"), outputs["ls_features"], targets, num_boxes, warm)
+            d, maps = self._masks_stacked(stacked("pred_masks"), stacked("pred_masks_low"), outputs["ls_features"], targets, num_boxes, warm, pack)
             per_layer.update(d)
         order = [k for k in ("loss_ce", "loss_bbox", "loss_giou", "loss_proj", "loss_mask", "loss_lst", "loss_proj_low", "loss_mask_low",
                              "loss_lst_low") if k in per_layer]

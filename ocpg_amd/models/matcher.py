@@ -11,7 +11,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..util.box_ops import box_cxcywh_to_xyxy
-from ..util.misc import nested_tensor_from_tensor_list
+from .ops.functions.target_pack_func import matcher_targets
 
 
 def _pairwise_giou_1(boxes, tgt):
@@ -69,22 +69,21 @@ class HungarianMatcher(nn.Module):
         self.mask_out_stride = 2
 
     @torch.no_grad()
-    def cost_matrix_stacked(self, logits, boxes, masks, targets):
+    def cost_matrix_stacked(self, logits, boxes, masks, targets, pack=None):
         """Matching cost of every query against the clip's single target for Lr decoder layers at once.
-        logits [Lr,B,T,q,K], boxes [Lr,B,T,q,4], masks [Lr,B,T,q,h,w] -> [Lr,B,q]."""
+        logits [Lr,B,T,q,K], boxes [Lr,B,T,q,4], masks [Lr,B,T,q,h,w] -> [Lr,B,q].  pack: the target pack built from these very
+        `targets` at this matcher's stride (ops/functions/target_pack_func.py), else the matcher derives its share itself."""
         with torch.autocast(device_type=masks.device.type, enabled=False):
             logits, boxes, masks = logits.float(), boxes.float(), masks.float()
             lr, bs, nf, nq, h, w = masks.shape
-            gt, _ = nested_tensor_from_tensor_list([t["masks"] for t in targets], size_divisibility=32, split=False).decompose()
-            gt = gt.to(masks)
             s = self.mask_out_stride
-            im_h, im_w = gt.shape[-2:]
-            gt = gt[:, :, s // 2::s, s // 2::s]
-            assert gt.size(2) * s == im_h and gt.size(3) * s == im_w
-
-            valid = torch.stack([t["valid"] for t in targets]).to(logits.dtype)                  # [B, T]
+            if pack is not None and pack.targets is targets and pack.key[2] == s:
+                gt, valid, tb, labels = pack.gt_m, pack.valid_f, pack.tboxes, pack.labels
+            else:
+                gt, valid, tb, labels = matcher_targets(targets, s, labels=self.num_classes != 1)
+                gt, valid, tb = gt.to(masks), valid.to(logits.dtype), tb.to(boxes.dtype)
             if masks.is_cuda and HIP_MATCHER:
-                return self._cost_matrix_hip(logits, boxes, masks, gt, valid, targets)
+                return self._cost_matrix_hip(logits, boxes, masks, gt, valid, tb, None if self.num_classes == 1 else labels)
             prob = logits.sigmoid()                                                              # [Lr, B, T, q, K]
             alpha, gamma = 0.25, 2.0
             neg = (1 - alpha) * (prob ** gamma) * (-(1 - prob + 1e-8).log())
@@ -92,11 +91,10 @@ class HungarianMatcher(nn.Module):
             if self.num_classes == 1:
                 cls = (pos - neg)[..., 0]                                                         # [Lr, B, T, q]
             else:
-                ids = torch.stack([t["labels"] for t in targets])                                # [B, T]
+                ids = labels                                                                      # [B, T]
                 cls = torch.gather(pos - neg, 4, ids[None, :, :, None, None].expand(lr, -1, -1, nq, 1))[..., 0]
             cost_class = (cls * valid[None, :, :, None]).sum(2) / valid.sum(1)[None, :, None]    # mean over valid frames
 
-            tb = torch.stack([t["boxes"] for t in targets]).to(boxes.dtype)                      # [B, T, 4]
             cost_bbox = (boxes - tb[None, :, :, None, :]).abs().sum(-1).mean(2)                  # [Lr, B, q]
             pb, tbx = box_cxcywh_to_xyxy(boxes), box_cxcywh_to_xyxy(tb)
             _assert_well_formed(pb, "predictions")
@@ -114,15 +112,15 @@ class HungarianMatcher(nn.Module):
             return (self.cost_class * cost_class + self.cost_bbox * cost_bbox + self.cost_giou * cost_giou
                     + self.cost_mask * cost_mask + self.cost_dice * cost_dice)
 
-    def _cost_matrix_hip(self, logits, boxes, masks, gt, valid, targets):
+    def _cost_matrix_hip(self, logits, boxes, masks, gt, valid, tb, labels):
         """One launch of csrc/matcher.hip for all layers, clips and queries."""
         from .._lib import check, lib
         lr, bs, nf, nq, h, w = masks.shape
         if masks.stride(-1) != 1 or masks.stride(-2) != w:
             masks = masks.contiguous()
         logits, boxes, gt = logits.contiguous(), boxes.contiguous(), gt.contiguous()
-        tb = torch.stack([t["boxes"] for t in targets]).to(boxes.dtype).contiguous()
-        labels = None if self.num_classes == 1 else torch.stack([t["labels"] for t in targets]).to(torch.int64).contiguous()
+        tb = tb.contiguous()
+        labels = None if labels is None else labels.contiguous()
         flag = _BOX_ERRORS.get(masks.device)
         if flag is None and not torch.cuda.is_current_stream_capturing():
             flag = _BOX_ERRORS[masks.device] = torch.zeros((), dtype=torch.int32, device=masks.device)
@@ -143,9 +141,9 @@ class HungarianMatcher(nn.Module):
         return self.cost_matrix_stacked(outputs["pred_logits"][None], outputs["pred_boxes"][None], outputs["pred_masks"][None], targets)[0]
 
     @torch.no_grad()
-    def match_stacked(self, logits, boxes, masks, targets):
+    def match_stacked(self, logits, boxes, masks, targets, pack=None):
         """-> int64 [Lr, B]: argmin query per clip and layer (one sync-free tensor program for all decoder layers)."""
-        return self.cost_matrix_stacked(logits, boxes, masks, targets).argmin(dim=2)
+        return self.cost_matrix_stacked(logits, boxes, masks, targets, pack).argmin(dim=2)
 
     @staticmethod
     def as_indices(src):

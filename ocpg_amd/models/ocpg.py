@@ -26,7 +26,8 @@ from torch import nn
 from ..util.misc import NestedTensor, inverse_sigmoid, nested_tensor_from_videos_list, resize_mask
 from . import amp_cache
 from .backbone import build_backbone
-from .criterion import SetCriterion
+from .criterion import MASK_OUT_STRIDE, MASK_OUT_STRIDE_LOW, SetCriterion
+from .ops.functions.target_pack_func import CRITERION_KEYS, build_target_pack
 from .decoder import MSO
 from .deformable_transformer import build_deforamble_transformer
 from .matcher import build_matcher
@@ -369,8 +370,14 @@ class OCPG(nn.Module):
             # in-forward matching (ocpg.py:352-366), all decoder layers in ONE tensor program
             shuffled = sh_all.permute(2, 0, 1, 3, 4, 5)                               # [l, b, t, q, 4h, 4w] (view)
             with torch.no_grad():
+                pack = None
+                if self.aux_loss and all(k in targets[0] for k in CRITERION_KEYS):
+                    # everything the matcher and the criterion derive from the targets alone, once per forward (csrc/target_pack.hip);
+                    # the criterion takes it only for this very `targets` list
+                    pack = out["_target_pack"] = build_target_pack(targets, MASK_OUT_STRIDE, MASK_OUT_STRIDE_LOW, self.matcher.mask_out_stride,
+                                                                   (4 * tar[0], 4 * tar[1]))
                 if self.aux_loss:
-                    src_all = self.matcher.match_stacked(outputs_class, outputs_coord, shuffled, targets)      # [l, b]
+                    src_all = self.matcher.match_stacked(outputs_class, outputs_coord, shuffled, targets, pack)      # [l, b]
                 else:
                     src_all = self.matcher.match_stacked(outputs_class[-1:], outputs_coord[-1:], shuffled[-1:], targets)
                 out["pred_masks"] = seg_masks_shuffled[-1]
