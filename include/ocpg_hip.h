@@ -885,6 +885,35 @@ int ocpg_target_pack_f32(int B, int T, const void* const* masks, const void* con
                          float* region_ls, float* weak_s, float* weak_l, float* w_s, float* w_l, float* tboxes, float* valid_f,
                          long long* valid_i, long long* labels_out, void* workspace, void* stream);
 
+/* Input front end of a clip (csrc/clip_front.hip): Pillow's 8-bit bilinear Image.resize of a crop window,
+ * byte for byte, fused with the horizontal flip, ToTensor + Normalize and the write into a (padded, strided) destination.  Reference:
+ * torchvision F.resize on a PIL image (datasets/transforms_video.py) = Image.resize((w, h), BILINEAR) = a horizontal pass, then a
+ * vertical pass, each rounded to uint8.
+ *   src           P = T*3 uint8 planes of src_h x src_w: plane p, row y, column x at src[p * src_plane + y * src_row + x] (strides in
+ *                 bytes; no alignment needed).  The resized image is the window rows top .. top+win_h-1, columns left .. left+win_w-1
+ *                 (a crop that was made BEFORE the resize: the taps stop at the window's edges, not the frame's).
+ *   Per axis      bounds int32 [out, 2] = (first tap, number of taps) relative to the window, coefs int32 [out, ks] = the taps'
+ *                 weights times 2^22, rounded (zero beyond the number of taps); device memory, built on the host in fp64
+ *                 (models/ops/functions/clip_front_func.py:resample_tables).  by / ky / ksy: rows; bx / kx / ksx: columns.
+ *   Per pass      out = clip_0_255((2^21 + sum_k in[first + k] * coef[k]) >> 22) in int32; the horizontal pass' bytes feed the vertical.
+ *   flip          0 / 1: output column x is written to column out_w - 1 - x.
+ *   mode 0        dst uint8: the byte.      mode 1        dst fp32: lut[(p % 3) * 256 + byte]  (lut fp32 [3 * 256], device memory).
+ *   dst           plane p, row y, column x at dst + p * dst_plane + y * dst_row + x, strides in ELEMENTS.  Exactly out_h x out_w
+ *                 elements per plane are written, nothing else (the padding of a batch tensor stays as it is).  Only the element
+ *                 type's alignment is needed; 4 elements per store wherever their address allows.
+ *   tile_rows     output rows per workgroup, one of 16, 8, 4, 2, 1;  cap_rows: at least the source rows any such tile of tile_rows
+ *                 output rows spans (first tap of its first row .. last tap of its last row); cap_rows * 64 bytes of LDS, at most
+ *                 32 KiB.  A tile that needs more than cap_rows rows is computed from the first cap_rows (wrong values, no wild access).
+ * One launch, integer arithmetic before the table look-up, no atomics, no intermediate in global memory, sizes by value: capturable.
+ * Return codes, all before any launch: P, a size or a stride <= 0, ksy / ksx <= 0: -1006;  window outside the frame: -2401;  flip
+ * outside 0..1: -2402;  mode outside 0..1: -2403;  tile_rows not one of 16 .. 1: -2404;  cap_rows <= 0 or cap_rows * 64 > 32768: -2405;
+ * a table NULL: -2406;  lut NULL in mode 1: -2407;  dst not aligned to its element: -2408;  P > 65535 or more than 65535 row tiles:
+ * -1008;  src NULL: -1001;  dst NULL: -1015. */
+int ocpg_clip_front_u8(const unsigned char* src, int P, long long src_plane, long long src_row, int src_h, int src_w, int top, int left,
+                       int win_h, int win_w, const int* by, const int* ky, int ksy, const int* bx, const int* kx, int ksx, int out_h,
+                       int out_w, int flip, int mode, int tile_rows, int cap_rows, void* dst, long long dst_plane, long long dst_row,
+                       const float* lut, void* stream);
+
 /* library / build identification: returns e.g. "ocpg_hip gfx950 r1" */
 const char* ocpg_hip_version(void);
 

@@ -153,6 +153,8 @@ SIGNATURES = {
     "ocpg_text_gate_fwd_h16": [_vp] * 6 + [ctypes.c_float] + [_int] * 5 + [_vp, _int, _vp],
     "ocpg_text_gate_bwd_h16": [_vp] * 7 + [ctypes.c_float] + [_int] * 5 + [_vp, _vp, _vp, _int, _vp],
     "ocpg_mask_tail_f32": [_vp] + [_int] * 10 + [ctypes.c_float, ctypes.c_float, _int, _vp, _vp],
+    "ocpg_clip_front_u8": [_vp, _int, ctypes.c_longlong, ctypes.c_longlong] + [_int] * 6 + [_vp, _vp, _int, _vp, _vp, _int] + [_int] * 6
+                          + [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp],
     "ocpg_jf_counts_u8": [_vp, _vp] + [_int] * 8 + [_vp, _vp],
     "ocpg_refmask_counts_f32": [_vp] + [_int] * 5 + [_vp] * 4 + [_int, _int, ctypes.c_float, _int, _vp, _vp],
     "ocpg_sim_heat_workspace": [_int] * 4,

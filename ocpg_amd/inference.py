@@ -84,12 +84,14 @@ def merge_objects(masks, threshold=0.3, background=0.1):
 
 
 def write_expression_masks(model, root, split, out_dir, videos=None, exclude_split=None, threshold=0.5, clip_len=None, device=None,
-                           amp_dtype=None, transform=None, native=False):
+                           amp_dtype=None, transform=None, native=False, pil_exact=False):
     """Ref-YouTube-VOS style inference to files (reference inference_ytvos.py:168-245): for every video of the split and every
     expression, segment the whole video (one clip unless clip_len is given), threshold the probabilities at `threshold` and write
     <out_dir>/Annotations/<video>/<exp_id>/<frame>.png (8-bit, 0 / 255).  Returns the number of frames written.
     native=True: best-query mask head + the fused tail (csrc/mask_tail.hip, mode 1): the 0 / 255 bytes the PNG writer reads come
-    straight from the stride-4 logits."""
+    straight from the stride-4 logits.
+    pil_exact=True (without `transform`): the frames are resized as the reference's Pillow transform resizes them, byte for byte
+    (eval_pipeline(pil_exact=True): csrc/clip_front.hip, resize + normalise in one launch)."""
     import os
 
     from PIL import Image
@@ -97,7 +99,7 @@ def write_expression_masks(model, root, split, out_dir, videos=None, exclude_spl
     from .datasets.clip_transforms import eval_pipeline
     from .datasets.video_folders import expressions_of_split, read_frames
     data = expressions_of_split(root, split, exclude_split)
-    transform = transform or eval_pipeline()
+    transform = transform or eval_pipeline(pil_exact=pil_exact)
     device = device or next(model.parameters()).device
     written = 0
     for video in (videos if videos is not None else data.keys()):

@@ -132,6 +132,27 @@ def nested_tensor_from_videos_list(videos_list: List[Tensor], size_divisibility:
     return NestedTensor(out, tag_rect_mask(mask, valid_hw))
 
 
+def nested_tensor_from_u8_clips(clips_u8: List[Tensor], sizes, size_divisibility: int = 32, flips=None, windows=None) -> NestedTensor:
+    """uint8 clips [T_i, 3, H_i, W_i] straight into the padded, normalised batch: clip i's `windows[i]` = (top, left, h, w) (default:
+    the whole frame) resized to `sizes[i]` = (h, w) as Pillow resizes it, flipped where `flips[i]`, normalised and written into its
+    slot of the [B, T, 3, PH, PW] zeros by one clip_front launch -- what nested_tensor_from_videos_list builds from the per-clip
+    results, without those results."""
+    from ..models.ops.functions.clip_front_func import clip_front
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    t = max(v.shape[0] for v in clips_u8)
+    h = _ceil_to(max(s[0] for s in sizes), size_divisibility)
+    w = _ceil_to(max(s[1] for s in sizes), size_divisibility)
+    dev = clips_u8[0].device
+    out = torch.zeros((len(clips_u8), t, 3, h, w), dtype=torch.float32, device=dev)
+    mask = torch.ones((len(clips_u8), t, h, w), dtype=torch.bool, device=dev)
+    for i, (v, (oh, ow)) in enumerate(zip(clips_u8, sizes)):
+        clip_front(v, (oh, ow), window=None if windows is None else windows[i], flip=bool(flips[i]) if flips is not None else False,
+                   normalize=True, out=out[i, : v.shape[0], :, :oh, :ow])
+        mask[i, : v.shape[0], :oh, :ow] = False
+    valid_hw = [sizes[i] if j < v.shape[0] else (0, 0) for i, v in enumerate(clips_u8) for j in range(t)]
+    return NestedTensor(out, tag_rect_mask(mask, valid_hw))
+
+
 def collate_fn(batch):
     """(clips, targets) pairs -> (NestedTensor padded to /32, tuple of targets); util/misc.py:299-307."""
     clips, targets = zip(*batch)
