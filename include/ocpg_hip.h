@@ -914,6 +914,59 @@ int ocpg_clip_front_u8(const unsigned char* src, int P, long long src_plane, lon
                        int out_w, int flip, int mode, int tile_rows, int cap_rows, void* dst, long long dst_plane, long long dst_row,
                        const float* lut, void* stream);
 
+/* Memory fusion of the mask head, read from the encoder output as it lies (csrc/mask_front.hip; the torch
+ * composition it stands for: ocpg.py `sum(bicubic_resize(x.float(), tar) for x in memory)` on the NCHW copies of the memory's levels).
+ *   memory [N, S, C] fp32, token-major: level l is an [h_l, w_l, C] channels-last block at token start_l; the levels tile the S tokens.
+ *   fusion = x_0 + sum_{1 <= l < n_lvl} My_l x_l Mx_l^T per channel, at level 0's size.
+ *   wts           the dense fp32 matrices My_l [h_0, h_l] and Mx_l [w_0, w_l] (resample.bicubic_matrix) of the levels 1 .. n_lvl-1;
+ *   rng           int32 pairs (first, count) of the entries of those matrices that are not zero: per output row / column the range of
+ *                 source indices (fy [h_0], fx [w_0]) and per source row / column the range of output indices (by [h_l], bx [w_l]).
+ *                 The kernels clamp every pair into its axis; entries outside a stated range are taken as zero.
+ *   geom_host     HOST array [n_lvl_total, 9] int64: h_l, w_l, start_l, then the offsets of My_l, Mx_l in wts (floats) and of fy, fx,
+ *                 by, bx in rng (ints); the offsets of level 0 and of the levels >= n_lvl are not read.  Passed by value to the kernels.
+ *   wts_len, rng_len: the elements wts and rng hold (every table is checked to lie inside).
+ *   Forward       out_nchw [N, C, h_0, w_0] and out_cl [N, h_0, w_0, C], either may be NULL (not both): the same numbers in two layouts.
+ *   Backward      g_nchw / g_cl: the gradients of the two ports, either may be NULL (not both), summed in registers;
+ *                 g_memory [N, S, C], every element written: the transposed resampling in gather form for the levels read, zeros for
+ *                 the others.  No atomics, sums in a fixed order: the same bits on every call.
+ * One launch each, no memset, sizes by value: capturable.
+ * Served (else -2000, before any launch): C % 4 == 0; n_lvl_total <= 6; h_l <= h_0 and w_l <= w_0 for the levels read; N <= 65535;
+ *   the row tiles fit 64 KiB of LDS (forward 256 * (sum_{l>=1} w_l + w_0 rounded up to 16 k + 1) bytes, backward 272 * w_0).
+ * Return codes, all before any launch: memory (forward) NULL or not 16-byte aligned, both gradients NULL or g_cl not aligned
+ *   (backward): -1001;  wts or rng NULL with n_lvl > 1: -1002;  geom_host NULL, a size <= 0 or > 65535, levels that do not tile the S
+ *   tokens, a table outside wts / rng: -1004;  n_lvl_total < 1 or n_lvl outside 1 .. n_lvl_total: -1005;  N <= 0: -1007;  S <= 0: -1008;
+ *   C <= 0: -1009;  both outputs NULL (forward), g_memory NULL or not aligned (backward): -1012;  out_cl not aligned: -1013. */
+int ocpg_memfuse_fwd_f32(const float* memory, const float* wts, const int* rng, const long long* geom_host, long long wts_len,
+                         long long rng_len, int n_lvl_total, int n_lvl, int N, int S, int C, float* out_nchw, float* out_cl, void* stream);
+int ocpg_memfuse_bwd_f32(const float* g_nchw, const float* g_cl, const float* wts, const int* rng, const long long* geom_host,
+                         long long wts_len, long long rng_len, int n_lvl_total, int n_lvl, int N, int S, int C, float* g_memory,
+                         void* stream);
+
+/* Level-set feature stack of the mask head (csrc/mask_front.hip; the torch lines it stands for: ocpg.py,
+ * bilinear x4 of ls_feat_viz's output, sim, the bilinear resize of the frames, cat).
+ *   lsf [B*T, h, w, 8] channels-last, fp32 / bf16 / fp16 (lsf_dtype 0 / 1 / 2), 16-byte aligned, widened on load; txt [B, 8] fp32;
+ *   frames [B*T, 3, H, W] fp32.  out [B*T, 12, Ho, Wo] fp32, every element written: channels 0-2 the frames and 3-10 lsf, bilinear with
+ *   the two-tap tables; 11: sim = (f . t) / (f / max(|f|, 1e-12) . t / max(|t|, 1e-12) + 1e-5) with f = channels 3-10 of the pixel.
+ *   tab_i / tab_w  device tables built from resample.bilinear_matrix: per output index the first source index (int) and the two matrix
+ *                 entries (float; the second tap is the next index, clamped); by / bx: per source row / column of lsf the (first,
+ *                 count) of the fine rows / columns with a non-zero entry.  off_host [12] (host): the int offsets of ly_i [Ho],
+ *                 lx_i [Wo], fy_i [Ho], fx_i [Wo], by [h, 2], bx [w, 2] in tab_i, the float offsets of ly_w [Ho, 2], lx_w [Wo, 2],
+ *                 fy_w, fx_w in tab_w, and the lengths of tab_i and tab_w.  Every index read from a table is clamped into its axis.
+ *   Backward      g [B*T, 12, Ho, Wo] fp32 (channels 0-2 are not read: the frames get no gradient).  g_lsf [B*T, h, w, 8] fp32, every
+ *                 element written, gather form; g_txt_part [B, ocpg_lsfeat_bwd_parts(T, Ho, Wo), 8] fp32, every element written: the
+ *                 caller sums over the parts.  Channel 11 of g is honoured wherever it is not zero; where it is zero nothing of the sim
+ *                 chain is evaluated and the txt gradient is exactly 0.  No atomics: the same bits on every call.
+ * One launch each, no memset, sizes by value: capturable.  Served (else -2000): B*T <= 65535, Ho*Wo < 2^31, 8 channels.
+ * Return codes, all before any launch: lsf NULL or not aligned: -1001;  lsf_dtype outside 0..2: -1002;  txt NULL: -1003;  a table or
+ *   off_host NULL, a table outside tab_i / tab_w: -1004;  B or T <= 0: -1005;  a size <= 0: -1006;  frames (forward) or g (backward)
+ *   NULL: -1007;  an output NULL: -1012. */
+int ocpg_lsfeat_fwd_f32(const void* lsf, int lsf_dtype, const float* txt, const float* frames, const int* tab_i, const float* tab_w,
+                        const long long* off_host, int B, int T, int h, int w, int H, int W, int Ho, int Wo, float* out, void* stream);
+int ocpg_lsfeat_bwd_parts(int T, int Ho, int Wo);
+int ocpg_lsfeat_bwd_f32(const float* g, const void* lsf, int lsf_dtype, const float* txt, const int* tab_i, const float* tab_w,
+                        const long long* off_host, int B, int T, int h, int w, int Ho, int Wo, float* g_lsf, float* g_txt_part,
+                        void* stream);
+
 /* library / build identification: returns e.g. "ocpg_hip gfx950 r1" */
 const char* ocpg_hip_version(void);
 

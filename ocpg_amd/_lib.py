@@ -161,6 +161,11 @@ SIGNATURES = {
     "ocpg_sim_heat_f32": [_vp] + [_int] * 5 + [_vp] * 10,
     "ocpg_target_pack_workspace": [_int],
     "ocpg_target_pack_f32": [_int, _int] + [_vp] * 8 + [_int] * 7 + [_vp] * 15,
+    "ocpg_memfuse_fwd_f32": [_vp] * 4 + [ctypes.c_longlong] * 2 + [_int] * 5 + [_vp] * 3,
+    "ocpg_memfuse_bwd_f32": [_vp] * 5 + [ctypes.c_longlong] * 2 + [_int] * 5 + [_vp] * 2,
+    "ocpg_lsfeat_fwd_f32": [_vp, _int] + [_vp] * 5 + [_int] * 8 + [_vp, _vp],
+    "ocpg_lsfeat_bwd_parts": [_int] * 3,
+    "ocpg_lsfeat_bwd_f32": [_vp, _vp, _int] + [_vp] * 4 + [_int] * 6 + [_vp, _vp, _vp],
     "ocpg_win_attn_fwd": [_vp, _vp, _vp, ctypes.c_float] + [_int] * 5 + [_vp, _vp, _int, _vp],
     "ocpg_win_attn_bwd": [_vp, _vp, _vp, _vp, ctypes.c_float] + [_int] * 5 + [_vp] * 6 + [_int, _vp],
     "ocpg_win_attn_bwd_mfma": [_vp, _vp, _vp, _vp, ctypes.c_float] + [_int] * 5 + [_vp] * 6 + [_int, _vp],
@@ -171,7 +176,7 @@ SIGNATURES = {
 
 # ---- optional live kernel timing (bench.py): HIP events on the launch stream around every library call ----------
 _TIMING = {"on": False, "events": []}
-_UNTIMED = ("ocpg_sim_heat_workspace", "ocpg_text_gate_rows", "ocpg_text_gate_splits", "ocpg_win_attn_dtable_supported", "ocpg_conv3x3_mfma_body_splits", "ocpg_gemm_dgrad_bn_tile", "ocpg_conv3x3_mfma_wgrad_splits", "ocpg_window_sums3x3_cl_bands", "ocpg_lfm_dft_supported", "ocpg_lfm_dft_split", "ocpg_conv3x3_mfma_splits", "ocpg_gemm_set_tuning", "ocpg_gemm_export_picks", "ocpg_gemm_import_picks", "ocpg_colsum_blocks", "ocpg_mso_wgrad_rows", "ocpg_gemm_plans", "ocpg_gemm_tuned", "ocpg_gemm_tune_rejected", "ocpg_bias_relu_dropout_bwd_slots", "ocpg_dropout_add_ln_bwd_slots", "ocpg_groupnorm_cl_work")
+_UNTIMED = ("ocpg_lsfeat_bwd_parts", "ocpg_sim_heat_workspace", "ocpg_text_gate_rows", "ocpg_text_gate_splits", "ocpg_win_attn_dtable_supported", "ocpg_conv3x3_mfma_body_splits", "ocpg_gemm_dgrad_bn_tile", "ocpg_conv3x3_mfma_wgrad_splits", "ocpg_window_sums3x3_cl_bands", "ocpg_lfm_dft_supported", "ocpg_lfm_dft_split", "ocpg_conv3x3_mfma_splits", "ocpg_gemm_set_tuning", "ocpg_gemm_export_picks", "ocpg_gemm_import_picks", "ocpg_colsum_blocks", "ocpg_mso_wgrad_rows", "ocpg_gemm_plans", "ocpg_gemm_tuned", "ocpg_gemm_tune_rejected", "ocpg_bias_relu_dropout_bwd_slots", "ocpg_dropout_add_ln_bwd_slots", "ocpg_groupnorm_cl_work")
 
 
 def enable_kernel_timing(on=True):

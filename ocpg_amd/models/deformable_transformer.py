@@ -19,6 +19,7 @@ from ..util.misc import fully_valid, inverse_sigmoid, mask_key, memo
 from . import amp_cache
 from .attention import MultiheadAttention
 from .ops.functions import fused_ln_func
+from .ops.functions import mask_front_func
 from .ops.modules import MSDeformAttn
 from .ops.modules.ms_deform_attn import resolve_value_dtype
 
@@ -434,10 +435,11 @@ class DeformableTransformer(nn.Module):
         # next layer's reference points): the model's box head re-uses these instead of running the same three GEMMs again.
         # Consumed here so that no autograd graph stays referenced from the module between steps.
         box_deltas, self.decoder.box_deltas = (self.decoder.box_deltas if self.decoder.return_intermediate else None), None
-        feats, start = [], 0
-        for (h, w) in shapes_host[: self.num_feature_level - 1]:
-            feats.append(memory[:, start:start + h * w].reshape(b * t, h, w, c).permute(0, 3, 1, 2).contiguous())
-            start += h * w
+        # the levels the mask head fuses: the token-major memory with its host-side level shapes (csrc/mask_front.hip reads it as it
+        # lies); the NCHW copies are made only where someone still asks for them (switch off, CPU, a shape the kernel does not serve)
+        feats = mask_front_func.LevelMaps(memory, shapes_host, self.num_feature_level - 1)
+        if not (mask_front_func.ENABLED and memory.is_cuda):
+            feats = feats.maps()
         return hs, feats, reference_points, inter_refs, box_deltas, None, inter_samples
 
 

@@ -34,6 +34,8 @@ from .matcher import build_matcher
 from .modules import LFMResizeAdaptive
 from .ops.functions.dynmask_func import dynamic_mask
 from .ops.functions.groupnorm_func import GroupNorm
+from .ops.functions import mask_front_func
+from .ops.functions.mask_front_func import LevelMaps, lsfeat, memfuse
 from .position_encoding import PositionEmbeddingSine1D
 from .postprocessors import build_postprocessors
 from .resample import bicubic_resize, bilinear_resize, nearest_upsample
@@ -322,8 +324,17 @@ class OCPG(nn.Module):
         out["pred_logits"], out["pred_boxes"] = outputs_class[-1], outputs_coord[-1]
 
         # ---- dynamic-conv mask head ----
-        tar = memory[0].shape[-2:]
-        memory_fusion = sum(bicubic_resize(x.float(), tar) for x in memory)
+        fused = None
+        if isinstance(memory, LevelMaps) and self.training and memory.memory.dtype == torch.float32 and memory.memory.is_contiguous():
+            # one launch from the token-major memory (csrc/mask_front.hip): the NCHW map for the dynamic mask head and, when the
+            # level-set head's conv kernel will read it, the same numbers channels-last; None: shape not served
+            fused = memfuse(memory.memory, memory.shapes, len(memory), True, bool(self.aux_loss and LS_FEAT_N16))
+        if fused is not None:
+            tar = memory.shapes[0]
+            memory_fusion, memory_fusion_cl = fused
+        else:
+            tar = memory[0].shape[-2:]
+            memory_fusion, memory_fusion_cl = sum(bicubic_resize(x.float(), tar) for x in memory), None
         mask_features = memory_fusion.unflatten(0, (b, t))                         # [b, t, C, h, w]
         # all decoder layers in ONE head evaluation: the nl*q parameter sets of a frame sit next to each other ([b, t, l, q]),
         # the mask features are shared (the reference loops over the layers, ocpg.py:339-349)
@@ -332,7 +343,7 @@ class OCPG(nn.Module):
         refs = inter_references[..., :2].transpose(0, 1).reshape(b, t * nl * nq, 2)
         return SimpleNamespace(out=out, hs=hs, features=features, samples=samples, b=b, t=t, nl=nl, nq=nq, dev=dev, tar=tar,
                                inter_references=inter_references, outputs_class=outputs_class, outputs_coord=outputs_coord,
-                               memory_fusion=memory_fusion, mask_features=mask_features, params=params, refs=refs,
+                               memory_fusion=memory_fusion, memory_fusion_cl=memory_fusion_cl, mask_features=mask_features, params=params, refs=refs,
                                text_sentence=text_sentence)
 
     def _best_query_masks(self, s, targets):
@@ -386,15 +397,22 @@ class OCPG(nn.Module):
                     out["aux_outputs"] = self._set_aux_loss(outputs_class, outputs_coord, seg_masks_shuffled)
                     out["aux_matcher_index"] = [self.matcher.as_indices(src_all[i]) for i in range(nl - 1)]
             if self.aux_loss:
-                lsf = self._ls_feat(memory_fusion)
-                ls_feat = (bilinear_resize(lsf, (4 * lsf.shape[-2], 4 * lsf.shape[-1]), True) if lsf.is_cuda and MATMUL_BILINEAR
-                           else F.interpolate(lsf, scale_factor=4, mode="bilinear", align_corners=True))
-                ls_feat = ls_feat.unflatten(0, (b, t))                              # [b, t, 8, 4h, 4w]
-                txt = self.ls_text_proj(text_sentence)[:, None, :, None, None]
-                sim = (ls_feat * txt).sum(dim=2) / ((F.normalize(ls_feat, dim=2) * F.normalize(txt, dim=2)).sum(dim=2) + 1e-5)
-                img = (bilinear_resize(samples.tensors, tuple(ls_feat.shape[-2:]), True) if lsf.is_cuda and MATMUL_BILINEAR
-                       else F.interpolate(samples.tensors, ls_feat.shape[-2:], mode="bilinear", align_corners=True)).unflatten(0, (b, t))
-                ls_features = torch.cat([img, ls_feat, sim.unsqueeze(2)], dim=2)    # [b, t, 12, 4h, 4w]  (same for every query)
+                lsf = self._ls_feat(memory_fusion, s.memory_fusion_cl)
+                ls_features = None
+                if mask_front_func.ENABLED and lsf.is_cuda and lsf.shape[1] == 8:
+                    # bilinear x4 of lsf, sim, the resized frames and the cat in one launch each way (csrc/mask_front.hip); None: not served
+                    ls_features = lsfeat(lsf, self.ls_text_proj(text_sentence), samples.tensors, b, t, (4 * lsf.shape[-2], 4 * lsf.shape[-1]))
+                if ls_features is not None:
+                    img = ls_features[:, :, :3].detach()
+                else:
+                    ls_feat = (bilinear_resize(lsf, (4 * lsf.shape[-2], 4 * lsf.shape[-1]), True) if lsf.is_cuda and MATMUL_BILINEAR
+                               else F.interpolate(lsf, scale_factor=4, mode="bilinear", align_corners=True))
+                    ls_feat = ls_feat.unflatten(0, (b, t))                              # [b, t, 8, 4h, 4w]
+                    txt = self.ls_text_proj(text_sentence)[:, None, :, None, None]
+                    sim = (ls_feat * txt).sum(dim=2) / ((F.normalize(ls_feat, dim=2) * F.normalize(txt, dim=2)).sum(dim=2) + 1e-5)
+                    img = (bilinear_resize(samples.tensors, tuple(ls_feat.shape[-2:]), True) if lsf.is_cuda and MATMUL_BILINEAR
+                           else F.interpolate(samples.tensors, ls_feat.shape[-2:], mode="bilinear", align_corners=True)).unflatten(0, (b, t))
+                    ls_features = torch.cat([img, ls_feat, sim.unsqueeze(2)], dim=2)    # [b, t, 12, 4h, 4w]  (same for every query)
 
                 # the matched query of every layer: one gather over [l, b, t, q, ...]
                 seg = m_all.permute(2, 0, 1, 3, 4, 5, 6)                            # [l, b, t, q, 16, h, w] (view)
@@ -437,17 +455,18 @@ class OCPG(nn.Module):
         return out
 
     @torch.jit.unused
-    def _ls_feat(self, x):
+    def _ls_feat(self, x, x_cl=None):
         """ls_feat_viz (ocpg.py:71 of the reference: Conv2d(hidden, 8, 3, 1, 1)) on the GPU: the <= 16-output-channel MFMA kernels of
         csrc/mso.hip (forward, input gradient, weight + bias gradient) on the channels-last map, operands in the autocast dtype with fp32
-        accumulation as an autocast convolution has; the library convolution otherwise."""
+        accumulation as an autocast convolution has; the library convolution otherwise.  x_cl: x as [N, h, w, C] where the memory fusion
+        kernel has already written it (else one copy here)."""
         conv = self.ls_feat_viz
         if not (LS_FEAT_N16 and x.is_cuda and x.shape[0] <= 65535 and x.dtype in (torch.float32, torch.bfloat16, torch.float16)):
             return conv(x)
         from .decoder import _bias32, _nhwc, _tap_major
         from .ops.functions.mso_func import compute_code, conv3x3_n16
         cdt = compute_code(x.device.type)
-        y = conv3x3_n16(_nhwc(x), _tap_major(amp_cache.lookup(conv.weight), cdt), _bias32(conv.bias), cdt=cdt)       # [N, h, w, 8] fp32
+        y = conv3x3_n16(_nhwc(x) if x_cl is None else x_cl, _tap_major(amp_cache.lookup(conv.weight), cdt), _bias32(conv.bias), cdt=cdt)       # [N, h, w, 8] fp32
         y = y.permute(0, 3, 1, 2)
         return y if cdt == 0 else y.to(torch.get_autocast_dtype(x.device.type))          # an autocast convolution returns the autocast dtype
 
