@@ -967,6 +967,40 @@ int ocpg_lsfeat_bwd_f32(const float* g, const void* lsf, int lsf_dtype, const fl
                         const long long* off_host, int B, int T, int h, int w, int Ho, int Wo, float* g_lsf, float* g_txt_part,
                         void* stream);
 
+/* Forward of the frozen RoBERTa text encoder (csrc/roberta.hip): fp32 storage and arithmetic, no backward.
+ * One launch each, no memset, no workspace, sizes by value: capturable.  No atomics but the integer `bad` counter.
+ *
+ * ocpg_roberta_embed_ln_f32: out [B, L, C] = LayerNorm(word[ids[b, l]] + type0 + pos[position(b, l)]) with gamma, beta [C], eps.
+ *   ids [B, L] int64; word [V, C], pos [P, C], type0 [C] (row 0 of the token-type table); all float tensors 16-byte aligned.
+ *   position(b, l) = pad_id + #{j <= l : ids[b, j] != pad_id} where ids[b, l] != pad_id, else pad_id (HF's
+ *   create_position_ids_from_input_ids: interior pads do not advance the count); the count is formed inside the kernel.
+ *   LayerNorm is two-pass (mean, then the centred sum of squares), one wave per token, the row held in registers.
+ *   bad (may be NULL; the caller zeroes it): incremented once per token whose id is outside [0, V); such a token reads no row of
+ *   `word`, its word embedding is taken as zeros.  No id makes the kernel read out of bounds.
+ *   Served (else -2000): C % 4 == 0 and C <= 1024.  L + pad_id + 1 > P: -2501, nothing is launched (a row of L non-pad tokens would
+ *   read past the position table).  Other return codes, all before any launch: a size <= 0 (B, L may be 0: nothing to do) or pad_id
+ *   < 0: -1009;  ids NULL: -1001;  word / pos / type0 / gamma / beta NULL or not aligned: -1002 .. -1006;  out: -1014.
+ *
+ * ocpg_attn_hd64_fwd_f32: out [B, L, H*64] = softmax(q k^T scale + mask) v per (batch, head), head_dim 64.
+ *   qkv [B, L, 3, H, 64]: the output of ONE Linear with the stacked q / k / v weights, 16-byte aligned.  attend [B, L], uint8
+ *   (attend_i64 0) or int64 (attend_i64 1): non-zero = the key is attended (HF's attention_mask).  A key that is not attended has
+ *   probability exactly 0; a query row at such a position is computed like any other.  The score is the 64-term fp32 dot, then scaled.
+ *   Every (batch) row must attend at least one key (the caller checks; a row without one yields zeros, not NaN).
+ *   Served (else -2000): 1 <= L <= 128, 1 <= H <= 65535, B <= 65535.  One wave per query row, 16 queries per workgroup, K and V of the
+ *   (batch, head) in LDS as fp32 with padded rows (L * 133 + 768 floats: 70 KiB at L = 128).
+ *   Return codes: a negative size: -1005;  attend_i64 outside 0..1: -1003;  qkv NULL or not aligned: -1001;  attend NULL: -1002;
+ *   out NULL: -1008.
+ *
+ * ocpg_bias_act_f32: y [R, C] = act(x + bias[C]); bias may be NULL; y may BE x (not overlap it otherwise).
+ *   act 0: identity;  1: exact GELU 0.5 v (1 + erf(v / sqrt 2));  2: tanh.  4 elements per load / store when x and y are 16-byte aligned.
+ *   Return codes: R < 0 or C <= 0: -1003;  act outside 0..2: -1005;  x NULL: -1001;  y NULL: -1006. */
+int ocpg_roberta_embed_ln_f32(const long long* ids, const float* word, const float* pos, const float* type0, const float* gamma,
+                              const float* beta, float eps, int pad_id, int B, int L, int C, int V, int P, float* out, int* bad,
+                              void* stream);
+int ocpg_attn_hd64_fwd_f32(const float* qkv, const void* attend, int attend_i64, float scale, int B, int L, int H, float* out,
+                           void* stream);
+int ocpg_bias_act_f32(const float* x, const float* bias, long long R, int C, int act, float* y, void* stream);
+
 /* library / build identification: returns e.g. "ocpg_hip gfx950 r1" */
 const char* ocpg_hip_version(void);
 

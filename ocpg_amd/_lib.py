@@ -171,6 +171,9 @@ SIGNATURES = {
     "ocpg_win_attn_bwd_mfma": [_vp, _vp, _vp, _vp, ctypes.c_float] + [_int] * 5 + [_vp] * 6 + [_int, _vp],
     "ocpg_win_attn_dtable_supported": [_int] * 4,
     "ocpg_win_attn_bwd_mfma_dtable": [_vp, _vp, _vp, _vp, ctypes.c_float] + [_int] * 5 + [_vp] * 6 + [_int, _int, _vp, _vp, _int, _vp],
+    "ocpg_roberta_embed_ln_f32": [_vp] * 6 + [ctypes.c_float] + [_int] * 6 + [_vp, _vp, _vp],
+    "ocpg_attn_hd64_fwd_f32": [_vp, _vp, _int, ctypes.c_float] + [_int] * 3 + [_vp, _vp],
+    "ocpg_bias_act_f32": [_vp, _vp, ctypes.c_longlong, _int, _int, _vp, _vp],
 }
 
 

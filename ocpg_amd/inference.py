@@ -13,14 +13,23 @@ from .models.ops.functions.mask_tail_func import mask_binary, mask_labels, mask_
 @torch.no_grad()
 def _selected_clips(model, frames, expression, clip_len, amp_dtype):
     """The native clip loop: OCPG.forward_selected per clip -> (logits [T, k] of the best query, stride-4 mask logits [T, 2h, 2w],
-    their factor to the padded frame)."""
+    their factor to the padded frame).  A `str` expression is encoded ONCE (TextEncoder.precompute, under the clips' autocast state) and
+    every clip receives those tensors as a PrecomputedText: the same features the per-clip encoder calls produced, one call instead of
+    one per clip."""
     video_len, _, img_h, img_w = frames.shape
     size = torch.as_tensor([int(img_h), int(img_w)], device=frames.device)
     all_logits, all_low, up = [], [], 4
+    if isinstance(expression, str):
+        encoder = getattr(model, "text_encoder", None)
+        if getattr(encoder, "text_backbone", None) is not None and hasattr(encoder, "precompute"):
+            with torch.autocast(device_type=frames.device.type, dtype=amp_dtype, enabled=amp_dtype is not None):
+                expression = encoder.precompute([expression], frames.device)
+        else:
+            expression = [expression]                   # a model without an encoder of its own (stand-ins) reads the string itself
     for start in range(0, video_len, clip_len):
         imgs = frames[start:start + clip_len]
         with torch.autocast(device_type=frames.device.type, dtype=amp_dtype, enabled=amp_dtype is not None):
-            outputs = model.forward_selected([imgs], [expression] if isinstance(expression, str) else expression, [{"size": size}])
+            outputs = model.forward_selected([imgs], expression, [{"size": size}])
         up = outputs["mask_up"]
         all_logits.append(outputs["pred_logits"][0, :, 0])
         all_low.append(outputs["pred_masks_low"][0].float())

@@ -8,7 +8,9 @@ repository.  Here:
     captions are tokenised by a deterministic whitespace/hash tokenizer (synthetic benchmark use only);
   * callers may also pass PRECOMPUTED text features (a `PrecomputedText`), which is what the synthetic
     BASELINE configs #1-#4 use ("random text tokens").
-HF transformers is the same third-party dependency the reference uses; its arithmetic is not restated here.
+HF transformers is the same third-party dependency the reference uses.  By default its forward runs as it is; with the opt-in switch
+`args.text_encoder_native` (None -> the environment variable OCPG_TEXT_NATIVE, else off) the frozen encoder's forward runs on the
+project's own kernels from the SAME module's parameters (roberta_native.py).
 """
 import os
 import zlib
@@ -85,6 +87,8 @@ class TextEncoder(nn.Module):
         self.freeze_text_encoder = args.freeze_text_encoder
         self.tokenizer = None
         self.text_backbone = None
+        native = getattr(args, "text_encoder_native", None)
+        self.native = (os.environ.get("OCPG_TEXT_NATIVE", "0") not in ("", "0")) if native is None else bool(native)
         if getattr(args, "text_encoder_lazy", False):
             return      # synthetic / fixture use: features are supplied by the caller, no RoBERTa is built
         from transformers import RobertaConfig, RobertaModel
@@ -101,9 +105,20 @@ class TextEncoder(nn.Module):
                 p.requires_grad_(False)
 
     def _encode(self, texts, device):
+        if self.native:
+            from .roberta_native import encode
+            tok = self.tokenizer(texts)                 # host tensors: validated there, uploaded by the runner
+            features, sentence = encode(self.text_backbone, tok["input_ids"], tok["attention_mask"])
+            return features, sentence, tok["attention_mask"].to(device).ne(1).bool()
         tok = {k: v.to(device) for k, v in self.tokenizer(texts).items()}
         enc = self.text_backbone(**tok)
         return enc.last_hidden_state, enc.pooler_output, tok["attention_mask"].ne(1).bool()
+
+    @torch.no_grad()
+    def precompute(self, texts, device):
+        """Encode once, reuse many times (inference: one expression, many clips): the three tensors `forward` returns for `texts`, as
+        a PrecomputedText, from either encoder, without autograd."""
+        return PrecomputedText(*self.forward(texts, device))
 
     def forward(self, texts, device):
         if isinstance(texts, PrecomputedText):

@@ -23,7 +23,10 @@ def default_args(**over):
         text_encoder_lazy=True,
         # storage dtype of MSDeformAttn's value / out: None | "fp32" | "bf16" | "fp16" | "autocast" (opt-in 16-bit mode, a deviation from
         # the reference's fp32 op; None = the environment variable OCPG_MSDA_VALUE_DTYPE, else "fp32": models/ops/modules/ms_deform_attn.py)
-        msda_value_dtype=None)
+        msda_value_dtype=None,
+        # the frozen RoBERTa forward on the project's own kernels: None | False | True (opt-in; None = the environment variable
+        # OCPG_TEXT_NATIVE, else off: models/text_encoder/roberta_native.py)
+        text_encoder_native=None)
     for k, v in over.items():
         setattr(ns, k, v)
     return ns
