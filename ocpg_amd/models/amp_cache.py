@@ -19,6 +19,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from .._lib import DTYPE_CODE as _DT
 from .ops.functions import conv_gemm_func
 
 _ACTIVE = {}        # id(fp32 parameter) -> low-precision copy, valid inside one `scope`
@@ -169,7 +170,6 @@ def join_wgrad():
     if _side_pending.pop(cur.device, False):
         cur.wait_stream(_side_streams[cur.device])
 
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 _CHUNK = 2048
 _BIAS_CHUNK = 256
 

@@ -17,10 +17,9 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ...._lib import check, lib, stream_ptr
+from ...._lib import DTYPE_CODE as _DT, check, lib, stream_ptr
 from .fused_ln_func import _unpack
 
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 SMALLK_KEYS = 32        # csrc/attn_smallk.hip
 LONGK_LIMIT = 128       # csrc/attn_longk.hip
 MAX_KEYS = 40           # most keys routed to the HIP kernels by default: the largest measured key count at which the long-key path is
@@ -47,186 +46,84 @@ def supported(q, k, H, pdrop):
             and q.shape[1] <= 65535 and 0.0 <= pdrop < 1.0)
 
 
-class SmallKeyAttention(Function):
+def _launches(batch_first, B, Lq, Lk, C, H):
+    """The launches of one pass: per launch (batch entries it covers, element offsets of its q / out / dout / dq rows, k / v rows,
+    padding row, lse rows, dk / dv rows).  Sequence-first is one launch over B; batch-first (q [B, Lq, C] against k / v [Lk, B, C]) is
+    one launch per batch entry with B = 1 on the [L, 1, C] view of its rows."""
+    if not batch_first:
+        return [(B, 0, 0, 0, 0, 0)]
+    return [(1, b * Lq * C, b * C, b * Lk, b * Lq * H, b * Lk * C) for b in range(B)]
+
+
+def _at(t, offset):
+    return None if t is None else t.data_ptr() + offset * t.element_size()
+
+
+class ShortKeyAttention(Function):
+    """Both kernel families (up to SMALLK_KEYS keys: csrc/attn_smallk.hip, more: csrc/attn_longk.hip) in both layouts.
+
+    Sequence-first: q / k / v [L, B, C] with any row stride (`_rows`, no copy), dropout from (pdrop, rng).  Batch-first: q [B, Lq, C]
+    (the visual tokens of the text gate are the channels-last feature map itself, [b, (t h w), c]; putting them token-major and back
+    cost two transposing copies of the map each way), k / v stay [Lk, B, C] (row stride B * C per entry); no dropout.
+    The long-key forward's output is kept for the backward: D = sum_j p~_j dp~_j = dout . out per (token, head), so the backward sweeps
+    the key chunks once."""
+
     @staticmethod
-    def forward(ctx, q, k, v, key_pad, scale, H, pdrop, rng):
-        q, ldq = _rows(q)
-        k, ldk = _rows(k)
-        v, ldv = _rows(v)
-        Lq, B, C = q.shape
+    def forward(ctx, q, k, v, key_pad, scale, H, pdrop, rng, batch_first):
+        if batch_first:
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+            B, Lq, C = q.shape
+            ldq, ldk, ldv = C, B * C, B * C
+        else:
+            q, ldq = _rows(q)
+            k, ldk = _rows(k)
+            v, ldv = _rows(v)
+            Lq, B, C = q.shape
         Lk = k.shape[0]
         pad = None if key_pad is None else key_pad.to(torch.uint8).contiguous()
-        out = torch.empty((Lq, B, C), dtype=q.dtype, device=q.device)
-        lse = torch.empty((Lq, B, H), dtype=torch.float32, device=q.device)
+        out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        lse = torch.empty(q.shape[:2] + (H,), dtype=torch.float32, device=q.device)
         seed, offset, base = (0, 0, None) if pdrop <= 0 else _unpack(rng)
+        name = "ocpg_attn_smallk_fwd" if Lk <= SMALLK_KEYS else "ocpg_attn_longk_fwd"
+        fn = getattr(lib(), name)
         with torch.cuda.device(q.device):
-            rc = lib().ocpg_attn_smallk_fwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, None if pad is None else pad.data_ptr(),
-                                            float(scale), Lq, B, H, C // H, Lk, float(pdrop), seed, offset, base, out.data_ptr(), C,
-                                            lse.data_ptr(), _DT[q.dtype], stream_ptr())
-        check(rc, "ocpg_attn_smallk_fwd")
-        ctx.save_for_backward(q, k, v, pad, lse)
-        ctx.meta = (float(scale), H, float(pdrop), seed, offset, base, ldq, ldk, ldv)
+            for nb, oq, ok, op, ol, _ in _launches(batch_first, B, Lq, Lk, C, H):
+                rc = fn(_at(q, oq), ldq, _at(k, ok), ldk, _at(v, ok), ldv, _at(pad, op), float(scale), Lq, nb, H, C // H, Lk, float(pdrop),
+                        seed, offset, base, _at(out, oq), C, _at(lse, ol), _DT[q.dtype], stream_ptr())
+                check(rc, name)
+        ctx.save_for_backward(q, k, v, pad, lse, *((out,) if Lk > SMALLK_KEYS else ()))
+        ctx.meta = (float(scale), H, float(pdrop), seed, offset, base, ldq, ldk, ldv, batch_first, B, Lq)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dout):
-        q, k, v, pad, lse = ctx.saved_tensors
-        scale, H, pdrop, seed, offset, base, ldq, ldk, ldv = ctx.meta
-        Lq, B, C = q.shape
-        Lk = k.shape[0]
+        q, k, v, pad, lse, *out = ctx.saved_tensors                 # out: the long-key path only
+        scale, H, pdrop, seed, offset, base, ldq, ldk, ldv, batch_first, B, Lq = ctx.meta
+        Lk, C = k.shape[0], q.shape[2]
         dout = dout.contiguous()
-        dq = torch.empty((Lq, B, C), dtype=q.dtype, device=q.device)
-        dkv = torch.zeros((2, Lk, B, C), dtype=torch.float32, device=q.device)
+        dq = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        dkv = torch.zeros((2, B, Lk, C) if batch_first else (2, Lk, B, C), dtype=torch.float32, device=q.device)
+        dk, dv = dkv[0], dkv[1]
+        name = "ocpg_attn_longk_bwd" if out else "ocpg_attn_smallk_bwd"
+        fn = getattr(lib(), name)
         with torch.cuda.device(q.device):
-            rc = lib().ocpg_attn_smallk_bwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, None if pad is None else pad.data_ptr(),
-                                            dout.data_ptr(), C, lse.data_ptr(), scale, Lq, B, H, C // H, Lk, pdrop, seed, offset, base,
-                                            dq.data_ptr(), C, dkv[0].data_ptr(), dkv[1].data_ptr(), _DT[q.dtype], stream_ptr())
-        check(rc, "ocpg_attn_smallk_bwd")
-        dkv = dkv.to(k.dtype)
-        return dq, dkv[0], dkv[1], None, None, None, None, None
-
-
-class LongKeyAttention(Function):
-    """SmallKeyAttention for 33 .. 128 keys (csrc/attn_longk.hip).  The forward's output is kept for the backward: D = sum_j p~_j dp~_j
-    = dout . out per (token, head), so the backward sweeps the key chunks once."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, key_pad, scale, H, pdrop, rng):
-        q, ldq = _rows(q)
-        k, ldk = _rows(k)
-        v, ldv = _rows(v)
-        Lq, B, C = q.shape
-        Lk = k.shape[0]
-        pad = None if key_pad is None else key_pad.to(torch.uint8).contiguous()
-        out = torch.empty((Lq, B, C), dtype=q.dtype, device=q.device)
-        lse = torch.empty((Lq, B, H), dtype=torch.float32, device=q.device)
-        seed, offset, base = (0, 0, None) if pdrop <= 0 else _unpack(rng)
-        with torch.cuda.device(q.device):
-            rc = lib().ocpg_attn_longk_fwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, None if pad is None else pad.data_ptr(),
-                                           float(scale), Lq, B, H, C // H, Lk, float(pdrop), seed, offset, base, out.data_ptr(), C,
-                                           lse.data_ptr(), _DT[q.dtype], stream_ptr())
-        check(rc, "ocpg_attn_longk_fwd")
-        ctx.save_for_backward(q, k, v, pad, lse, out)
-        ctx.meta = (float(scale), H, float(pdrop), seed, offset, base, ldq, ldk, ldv)
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dout):
-        q, k, v, pad, lse, out = ctx.saved_tensors
-        scale, H, pdrop, seed, offset, base, ldq, ldk, ldv = ctx.meta
-        Lq, B, C = q.shape
-        Lk = k.shape[0]
-        dout = dout.contiguous()
-        dq = torch.empty((Lq, B, C), dtype=q.dtype, device=q.device)
-        dkv = torch.zeros((2, Lk, B, C), dtype=torch.float32, device=q.device)
-        with torch.cuda.device(q.device):
-            rc = lib().ocpg_attn_longk_bwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, None if pad is None else pad.data_ptr(),
-                                           dout.data_ptr(), C, out.data_ptr(), C, lse.data_ptr(), scale, Lq, B, H, C // H, Lk, pdrop, seed,
-                                           offset, base, dq.data_ptr(), C, dkv[0].data_ptr(), dkv[1].data_ptr(), _DT[q.dtype], stream_ptr())
-        check(rc, "ocpg_attn_longk_bwd")
-        dkv = dkv.to(k.dtype)
-        return dq, dkv[0], dkv[1], None, None, None, None, None
+            for nb, oq, ok, op, ol, od in _launches(batch_first, B, Lq, Lk, C, H):
+                saved_out = (_at(out[0], oq), C) if out else ()
+                rc = fn(_at(q, oq), ldq, _at(k, ok), ldk, _at(v, ok), ldv, _at(pad, op), _at(dout, oq), C, *saved_out, _at(lse, ol), scale,
+                        Lq, nb, H, C // H, Lk, pdrop, seed, offset, base, _at(dq, oq), C, _at(dk, od), _at(dv, od), _DT[q.dtype],
+                        stream_ptr())
+                check(rc, name)
+        if batch_first:
+            dkv = dkv.transpose(1, 2)                               # [2, Lk, B, C]
+        dkv = dkv.to(k.dtype)                                       # dk / dv accumulate in fp32 and are cast once
+        return dq, dkv[0], dkv[1], None, None, None, None, None, None
 
 
 def attention(q, k, v, key_padding_mask, scale, H, pdrop=0.0, rng=None):
     if not supported(q, k, H, pdrop):
         return None
-    fn = SmallKeyAttention if k.shape[0] <= SMALLK_KEYS else LongKeyAttention
-    return fn.apply(q, k, v, key_padding_mask, scale, H, pdrop, rng)
-
-
-class SmallKeyAttentionBF(Function):
-    """The same attention for queries stored BATCH-FIRST, q [B, Lq, C] (round 4: the visual tokens of the text gate are the channels-last
-    feature map itself, [b, (t h w), c]; putting them token-major and back cost two transposing copies of the map each way).  One launch
-    per batch entry on the [L, 1, C] view of its rows; k / v stay [Lk, B, C] (row stride B * C per entry, no copy).  No dropout."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, key_pad, scale, H):
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        B, Lq, C = q.shape
-        Lk = k.shape[0]
-        pad = None if key_pad is None else key_pad.to(torch.uint8).contiguous()
-        out = torch.empty((B, Lq, C), dtype=q.dtype, device=q.device)
-        lse = torch.empty((B, Lq, H), dtype=torch.float32, device=q.device)
-        es = q.element_size()
-        with torch.cuda.device(q.device):
-            for b in range(B):
-                rc = lib().ocpg_attn_smallk_fwd(q.data_ptr() + b * Lq * C * es, C, k.data_ptr() + b * C * es, B * C, v.data_ptr() + b * C * es, B * C,
-                                                None if pad is None else pad.data_ptr() + b * Lk, float(scale), Lq, 1, H, C // H, Lk, 0.0, 0, 0, None,
-                                                out.data_ptr() + b * Lq * C * es, C, lse.data_ptr() + b * Lq * H * 4, _DT[q.dtype], stream_ptr())
-                check(rc, "ocpg_attn_smallk_fwd")
-        ctx.save_for_backward(q, k, v, pad, lse)
-        ctx.meta = (float(scale), H)
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dout):
-        q, k, v, pad, lse = ctx.saved_tensors
-        scale, H = ctx.meta
-        B, Lq, C = q.shape
-        Lk = k.shape[0]
-        dout = dout.contiguous()
-        dq = torch.empty((B, Lq, C), dtype=q.dtype, device=q.device)
-        dkv = torch.zeros((2, B, Lk, C), dtype=torch.float32, device=q.device)
-        es = q.element_size()
-        with torch.cuda.device(q.device):
-            for b in range(B):
-                rc = lib().ocpg_attn_smallk_bwd(q.data_ptr() + b * Lq * C * es, C, k.data_ptr() + b * C * es, B * C, v.data_ptr() + b * C * es, B * C,
-                                                None if pad is None else pad.data_ptr() + b * Lk, dout.data_ptr() + b * Lq * C * es, C,
-                                                lse.data_ptr() + b * Lq * H * 4, scale, Lq, 1, H, C // H, Lk, 0.0, 0, 0, None,
-                                                dq.data_ptr() + b * Lq * C * es, C, dkv[0, b].data_ptr(), dkv[1, b].data_ptr(), _DT[q.dtype],
-                                                stream_ptr())
-                check(rc, "ocpg_attn_smallk_bwd")
-        dkv = dkv.transpose(1, 2).to(k.dtype)               # [2, Lk, B, C]
-        return dq, dkv[0], dkv[1], None, None, None
-
-
-class LongKeyAttentionBF(Function):
-    """SmallKeyAttentionBF for 33 .. 128 keys (csrc/attn_longk.hip): one launch per batch entry each way, the forward's output kept."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, key_pad, scale, H):
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        B, Lq, C = q.shape
-        Lk = k.shape[0]
-        pad = None if key_pad is None else key_pad.to(torch.uint8).contiguous()
-        out = torch.empty((B, Lq, C), dtype=q.dtype, device=q.device)
-        lse = torch.empty((B, Lq, H), dtype=torch.float32, device=q.device)
-        es = q.element_size()
-        with torch.cuda.device(q.device):
-            for b in range(B):
-                rc = lib().ocpg_attn_longk_fwd(q.data_ptr() + b * Lq * C * es, C, k.data_ptr() + b * C * es, B * C, v.data_ptr() + b * C * es, B * C,
-                                               None if pad is None else pad.data_ptr() + b * Lk, float(scale), Lq, 1, H, C // H, Lk, 0.0, 0, 0, None,
-                                               out.data_ptr() + b * Lq * C * es, C, lse.data_ptr() + b * Lq * H * 4, _DT[q.dtype], stream_ptr())
-                check(rc, "ocpg_attn_longk_fwd")
-        ctx.save_for_backward(q, k, v, pad, lse, out)
-        ctx.meta = (float(scale), H)
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dout):
-        q, k, v, pad, lse, out = ctx.saved_tensors
-        scale, H = ctx.meta
-        B, Lq, C = q.shape
-        Lk = k.shape[0]
-        dout = dout.contiguous()
-        dq = torch.empty((B, Lq, C), dtype=q.dtype, device=q.device)
-        dkv = torch.zeros((2, B, Lk, C), dtype=torch.float32, device=q.device)
-        es = q.element_size()
-        with torch.cuda.device(q.device):
-            for b in range(B):
-                rc = lib().ocpg_attn_longk_bwd(q.data_ptr() + b * Lq * C * es, C, k.data_ptr() + b * C * es, B * C, v.data_ptr() + b * C * es, B * C,
-                                               None if pad is None else pad.data_ptr() + b * Lk, dout.data_ptr() + b * Lq * C * es, C,
-                                               out.data_ptr() + b * Lq * C * es, C, lse.data_ptr() + b * Lq * H * 4, scale, Lq, 1, H, C // H, Lk,
-                                               0.0, 0, 0, None, dq.data_ptr() + b * Lq * C * es, C, dkv[0, b].data_ptr(), dkv[1, b].data_ptr(),
-                                               _DT[q.dtype], stream_ptr())
-                check(rc, "ocpg_attn_longk_bwd")
-        dkv = dkv.transpose(1, 2).to(k.dtype)               # [2, Lk, B, C]
-        return dq, dkv[0], dkv[1], None, None, None
+    return ShortKeyAttention.apply(q, k, v, key_padding_mask, scale, H, pdrop, rng, False)
 
 
 def attention_batch_first(q, k, v, key_padding_mask, scale, H):
@@ -234,5 +131,4 @@ def attention_batch_first(q, k, v, key_padding_mask, scale, H):
     if not (q.is_cuda and q.dtype in _DT and q.shape[-1] % H == 0 and q.shape[-1] // H == 32 and H <= 8 and 256 % H == 0
             and k.shape[0] <= key_limit()):
         return None
-    fn = SmallKeyAttentionBF if k.shape[0] <= SMALLK_KEYS else LongKeyAttentionBF
-    return fn.apply(q, k, v, key_padding_mask, scale, H)
+    return ShortKeyAttention.apply(q, k, v, key_padding_mask, scale, H, 0.0, None, True)

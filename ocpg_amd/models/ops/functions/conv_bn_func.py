@@ -15,10 +15,9 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ...._lib import check, lib
+from ...._lib import DTYPE_CODE as _DT, H16_CODE, check, lib
 
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
-_H16 = (torch.bfloat16, torch.float16)      # the 16-bit storage types of the own MFMA kernels (fp16: the reference's --amp mode)
+_H16 = H16_CODE.keys()      # the 16-bit storage types of the own MFMA kernels (fp16: the reference's --amp mode)
 _CL = torch.channels_last
 EPILOGUE = os.environ.get("OCPG_GEMM_EPILOGUE", "1") != "0"     # A/B switch: BN affine / skip / ReLU in the GEMM epilogue
 # A/B switch: the gradient of a bottleneck's identity skip is ADDED BY THE GEMM that computes conv1's input gradient (C = gz W + 1.0 C on
@@ -286,12 +285,9 @@ def conv1x1_bn_act(x, w, scale, shift, skip, relu, splits):
 
 
 # ---- 3x3 conv (padding == dilation, stride 1|2) + frozen BN + ReLU: im2col (HIP) -> GEMM with the BN/ReLU epilogue ---------
-_DT3 = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
-
-
 def eligible3x3(x, conv):
     """Where the patch-matrix GEMM beats MIOpen (tools/bench_conv3x3.py): >= 256 channels on maps of <= 12288 output pixels."""
-    if not (x.is_cuda and x.dim() == 4 and x.dtype in _DT3 and conv.kernel_size == (3, 3) and conv.groups == 1 and conv.bias is None
+    if not (x.is_cuda and x.dim() == 4 and x.dtype in _DT and conv.kernel_size == (3, 3) and conv.groups == 1 and conv.bias is None
             and conv.stride[0] == conv.stride[1] and conv.stride[0] in (1, 2) and conv.dilation[0] == conv.dilation[1]
             and conv.padding == conv.dilation and conv.padding_mode == "zeros" and x.is_contiguous(memory_format=_CL)):
         return False
@@ -307,7 +303,7 @@ class Conv3x3BNAct(Function):
         co = w.shape[0]
         ho, wo = (h - 1) // stride + 1, (wd - 1) // stride + 1
         m = n * ho * wo
-        dt = _DT3[x.dtype]
+        dt = _DT[x.dtype]
         L = lib()
         st = torch.cuda.current_stream().cuda_stream
         cols = torch.empty((m, 9 * c), dtype=x.dtype, device=x.device)
@@ -336,7 +332,7 @@ class Conv3x3BNAct(Function):
         relu, splits, (n, c, h, wd, ho, wo, stride, dil), wshape = ctx.meta
         co = w2.shape[0]
         m, k = cols.shape
-        dt = _DT3[y.dtype]
+        dt = _DT[y.dtype]
         L = lib()
         st = torch.cuda.current_stream().cuda_stream
         if gy.dtype != y.dtype or not gy.is_contiguous(memory_format=_CL):

@@ -9,10 +9,9 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ...._lib import check, lib, stream_ptr
+from ...._lib import DTYPE_CODE as _DT, check, lib, stream_ptr
 from .gemm_func import mm
 
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 ALWAYS = False      # tests: take the GEMM path for every eligible geometry, not only where it is faster
 
 

@@ -17,10 +17,9 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ...._lib import check, lib
+from ...._lib import DTYPE_CODE as _DT, check, lib
 from .gemm_func import mm
 
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 # A/B switch, read once: the extra ports of the dropout+add+LayerNorm kernels (y + addend and a 16-bit copy of y forward, up to three
 # gradient addends and the Linear's bias-gradient partials backward) and the Linear + dropout/add/LN autograd node; 0 = the plain calls
 PORTS = os.environ.get("OCPG_FUSED_LN_PORTS", "1") != "0"

@@ -3,11 +3,10 @@ import ctypes
 
 import torch
 
-from ...._lib import check, lib
+from ...._lib import DTYPE_CODE as _DT, check, lib
 
 import os
 
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 # A/B switch: the path's large GEMMs (token Linears, 1x1 / im2col convolutions, their gradients) through the plan cache, whose plans
 # are timed at first use (csrc/gemm.hip: tune()); "0" = torch.mm / addmm / bmm (hipBLASLt's first heuristic choice)
 PLANNED = os.environ.get("OCPG_PLANNED_GEMM", "1") != "0"

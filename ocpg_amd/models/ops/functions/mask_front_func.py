@@ -20,13 +20,12 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ...._lib import check, lib, stream_ptr
+from ...._lib import DTYPE_CODE as _DT, check, lib, stream_ptr
 from ...resample import bicubic_matrix, bilinear_matrix
 
 # A/B switch, read once: 1 = memory fusion and level-set feature stack by csrc/mask_front.hip on the GPU training path; 0 = the torch lines
 ENABLED = os.environ.get("OCPG_MASK_FRONT", "1") != "0"
 NOT_SERVED = -2000
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 _TABLES = OrderedDict()         # geometry -> device tables, least recently used first, at most _TABLES_MAX entries
 _TABLES_MAX = 64
 

@@ -11,7 +11,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ...._lib import check, lib, require_gpu, stream_ptr
+from ...._lib import H16_CODE as _H16, check, lib, require_gpu, stream_ptr      # _H16: 16-bit STORAGE of value / out / grad_out (ocpg_msda_*_h16)
 
 
 # -- optional live kernel timing (bench.py): events on the launch stream around every kernel call -----------------
@@ -65,10 +65,6 @@ def _dims(value, loc):
     N, S, M, D = value.shape
     _, Lq, _, L, P, _ = loc.shape
     return N, S, M, D, L, Lq, P
-
-
-# 16-bit STORAGE of value / out / grad_out (include/ocpg_hip.h: ocpg_msda_*_h16): the C ABI's dtype codes
-_H16 = {torch.bfloat16: 1, torch.float16: 2}
 
 
 def _check_h16(fn, value, sampling_loc, attn_weight):

@@ -10,9 +10,8 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ...._lib import check, lib
+from ...._lib import DTYPE_CODE as _DT, check, lib
 
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 _TORCH = {0: torch.float32, 1: torch.bfloat16, 2: torch.float16}
 
 

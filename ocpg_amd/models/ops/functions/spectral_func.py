@@ -3,7 +3,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ...._lib import check, lib
+from ...._lib import DTYPE_CODE as _DT, check, lib
 
 
 class SpectralGate(Function):
@@ -93,9 +93,6 @@ def conv3x3_valid_spatial_mean(x, weight, bias, as_bf16):
     m = WindowMeans3x3CL.apply(x, as_bf16) if cl else WindowMeans3x3.apply(x, as_bf16)
     with torch.autocast(device_type=x.device.type, enabled=False):
         return torch.nn.functional.linear(m, weight.float().flatten(1), None if bias is None else bias.float())
-
-
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 
 class SpectralGateCL(Function):

@@ -23,13 +23,12 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ...._lib import check, lib, stream_ptr
+from ...._lib import H16_CODE as _DT, check, lib, stream_ptr
 
 MODE = os.environ.get("OCPG_TEXT_GATE_FUSED", "1")                 # A/B switch, read once at import
 ENABLED = MODE != "0"               # 0 = the unfused calls and autograd nodes
 FUSED_FORWARD = MODE == "fwd"       # fwd = the forward through the kernel too; 1 (default): the forward keeps the unfused path's bits
 MAX_KEYS = 16
-_DT = {torch.bfloat16: 1, torch.float16: 2}
 
 
 class TextGateFunction(Function):

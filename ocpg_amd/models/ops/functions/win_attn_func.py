@@ -13,9 +13,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ...._lib import check, lib, stream_ptr
-
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+from ...._lib import DTYPE_CODE as _DT, check, lib, stream_ptr
 
 
 class WindowAttentionFunction(Function):

@@ -30,9 +30,12 @@ def test_h16_symbols_are_declared_and_bound():
 
 
 def test_python_dtype_codes():
+    from ocpg_amd import _lib
     from ocpg_amd.models.ops.functions import bn_act_func, conv_bn_func
-    for table in (bn_act_func._DT, conv_bn_func._DT, conv_bn_func._DT3):
-        assert table[torch.float32] == 0 and table[torch.bfloat16] == 1 and table[torch.float16] == 2
+    table = _lib.DTYPE_CODE
+    assert table[torch.float32] == 0 and table[torch.bfloat16] == 1 and table[torch.float16] == 2 and len(table) == 3
+    assert bn_act_func._DT is table and conv_bn_func._DT is table          # the bindings use that very table, not a copy
+    assert not hasattr(conv_bn_func, "_DT3")
 
 
 def test_fp16_is_not_eligible_where_a_switch_selects_a_bf16_only_kernel(monkeypatch):
