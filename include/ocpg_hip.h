@@ -617,6 +617,26 @@ int ocpg_lfm_spectrum_fwd(const float* x, const float* coef, const float* high, 
                           float norm, void* tmp, void* pair, int pair_dt, void* stream);
 int ocpg_lfm_spectrum_inv(const void* pair, int pair_dt, const float* coef, const float* high, const void* z_saved, float* coef_part, int N, int H,
                           int W, int C, const void* tw_h, const void* tw_w, float norm, void* tmp, const float* residual, float* out, void* stream);
+/* The same two transforms for EVERY length 1 <= H, W <= 256 (csrc/lfm_dft_any.hip): same arguments, same results and layouts as the two
+ * entries above, plus the PLAN of each axis by value -- up to three stages whose product is the length, unused stages 1 (anywhere):
+ * h1 * h2 * h3 == H, w1 * w2 * w3 == W.  A stage is <= 16, or ONE prime 17..251 per axis (the direct stage; every length <= 256 that
+ * is not a product of three stages <= 16 is such a prime times a stage <= 15).  With s0, s1, s2 the stages that are not 1, in the
+ * order given (missing ones 1), spectrum element k = k0 + s0 k1 + s0 s1 k2 leaves the line transform in slot (k0 s1 + k1) s2 + k2.
+ * tw_h / tw_w: the table of the axis' length L and plan, 2 * E floats + L ints: float2 [0, L) exp(-2 pi i m / L); then, for each stage
+ * s <= 16 that is not 1, in plan order, the s-point DFT matrix exp(-2 pi i j k / s) at [k * s + j] (a prime stage above 16 has none:
+ * it reads the first table); E = L + the sum of those s^2; then int32 [L]: the slot of spectrum element k.
+ * Lengths <= 128 run 64 channels per workgroup, 129..256 run 32: coef_part is [N, (W/2+1) * ceil(C / (H > 128 ? 32 : 64))]; tmp as above.
+ * Before any launch, writing nothing: N < 0, H, W, C < 1: -1003 (fwd) / -1007 (inv);  N == 0: 0;  a plan whose product is not the
+ * length, a length above 256, a stage < 1, a stage above 16 that is not a prime <= 251, or two such stages on one axis: -2000;  then the
+ * null-pointer / dtype codes of the entries above (fwd: x -1001, tw -1005, tmp -1011, pair -1012, coef xor high -1002, pair_dt -1013,
+ * N*H or N*(W/2+1) above 2^31-1 -1003; inv: pair -1001, tw -1011, tmp -1014, out -1016, coef xor high -1003, coef_part without coef /
+ * z_saved -1005, pair_dt -1002, sizes -1007).  fwd overwrites tmp and every element of pair; inv overwrites tmp, every element of out
+ * and, when given, every element of coef_part.  Two launches each, every size by value: capturable. */
+int ocpg_lfm_spectrum_fwd_any(const float* x, const float* coef, const float* high, int N, int H, int W, int C, const void* tw_h, const void* tw_w,
+                              float norm, void* tmp, void* pair, int pair_dt, int h1, int h2, int h3, int w1, int w2, int w3, void* stream);
+int ocpg_lfm_spectrum_inv_any(const void* pair, int pair_dt, const float* coef, const float* high, const void* z_saved, float* coef_part, int N, int H,
+                              int W, int C, const void* tw_h, const void* tw_w, float norm, void* tmp, const float* residual, float* out, int h1, int h2,
+                              int h3, int w1, int w2, int w3, void* stream);
 int ocpg_window_means3x3_fwd(const float* x, long long planes, int h, int w, int as_bf16, float* out, void* stream);
 int ocpg_window_means3x3_bwd(const float* gm, long long planes, int h, int w, float* dx, void* stream);
 /* The same on a channels-last map x [N, h, w, C] fp32 (round 4): part [N][ocpg_window_sums3x3_cl_bands(h)][C * 9] = window SUMS of a band of

@@ -10,16 +10,34 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..util.misc import memo
-from . import amp_cache
+from . import amp_cache, fallbacks
 import os
 
-from .ops.functions.spectral_func import (conv3x3_valid_spatial_mean, dft_supported, ifft2_real, lfm_inverse, lfm_spectrum, pair_to_complex,
-                                          spectral_gate, spectral_gate_cl)
+from .ops.functions.spectral_func import (conv3x3_valid_spatial_mean, dft_any_supported, dft_plan, dft_supported, ifft2_real, lfm_inverse, lfm_spectrum,
+                                          pair_to_complex, spectral_gate, spectral_gate_cl)
 
 FUSED_GATE = True       # A/B switch: fused spectral gate kernel
 GATE_NHWC = True        # A/B switch: gate output / inverse-FFT input in channels-last memory (1x1 convs as GEMMs, no casts / layout copies)
 DFT_CL = os.environ.get("OCPG_LFM_DFT", "1") != "0"       # A/B switch: both transforms by csrc/lfm_dft.hip on the channels-last map (else rocFFT between transposes)
-LAPLACE_MEAN = True     # A/B switch: mean(laplace(x)) as nine window means + one small matrix product (no convolution)
+# OCPG_LFM_DFT_ANY (default 1): a map csrc/lfm_dft.hip refuses (a length with a prime factor > 16, 125, or above 128) runs both transforms on
+# csrc/lfm_dft_any.hip instead of rocFFT; 0 restores the library route for those maps exactly.  DFT_ANY_MAX_PRIME: the largest prime factor
+# whose direct O(p^2) stage is not slower than the library route (measured, DESIGN 4.8x: profiles/lfm_dft_any_ab.jsonl); a map with a larger one
+# (or a length above 256) goes to the library and is counted in models/fallbacks.py.  The kernels themselves serve every prime up to 251.
+DFT_ANY = os.environ.get("OCPG_LFM_DFT_ANY", "1") != "0"
+DFT_ANY_MAX_PRIME = 79
+
+
+def dft_any_default(length):
+    """Does a line of this length take csrc/lfm_dft_any.hip by default?  Yes when its plan has stages <= 16 only (every such length up to 256
+    measured faster), or one prime stage <= DFT_ANY_MAX_PRIME in a length <= 128 (above 128 a workgroup runs 32 channels with half of each
+    wave idle in the stages, and the direct stage then loses to the library at every prime measured)."""
+    plan = dft_plan(length)
+    if plan is None:
+        return False
+    return max(plan) <= 16 or (max(plan) <= DFT_ANY_MAX_PRIME and length <= 128)
+
+
+LAPLACE_MEAN = True   # A/B switch: mean(laplace(x)) as nine window means + one small matrix product (no convolution)
 
 
 class LFMResizeAdaptive(nn.Module):
@@ -71,7 +89,13 @@ class LFMResizeAdaptive(nn.Module):
             high._ocpg_key = key
         if x.is_cuda and FUSED_GATE and GATE_NHWC and c % 4 == 0:
             dt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else torch.float32
-            if DFT_CL and dft_supported(h, w):
+            own = DFT_CL and dft_supported(h, w)
+            if not own and DFT_CL and DFT_ANY:
+                own = dft_any_supported(h, w) and dft_any_default(h) and dft_any_default(w)
+                if not own:         # the library route, counted (and an error under OCPG_STRICT_HIP=1); silent only with the switch off
+                    fallbacks.note("LFM", f"no own Fourier transform for a {h} x {w} map by default (a length above 256, a prime factor above "
+                                          f"{DFT_ANY_MAX_PRIME}, or one above 16 in a length above 128)", x)
+            if own:
                 z = lfm_spectrum(x, coef.float().reshape(b), high.reshape(h, w), dt)      # fft2 + gate + [Re || Im], channels-last
                 y = self.conv2(F.relu(self.conv1(z)))
                 return lfm_inverse(y, x), high                                          # x + ifft2(.).real

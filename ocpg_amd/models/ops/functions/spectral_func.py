@@ -1,4 +1,7 @@
-"""Autograd binding of csrc/spectral.hip: the LFM block's spectral gate as one pass each way."""
+"""Autograd binding of csrc/spectral.hip: the LFM block's spectral gate as one pass each way; of csrc/lfm_dft.hip and
+csrc/lfm_dft_any.hip: both Fourier transforms on the channels-last map, and the plan of every line length up to 256."""
+import functools
+
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -213,6 +216,99 @@ def _twiddles(n, device):
     return memo("lfm_tw", n, device, make)
 
 
+# ---- every length 1..256 (csrc/lfm_dft_any.hip) -------------------------------------------------------------------------------
+MAX_ANY = 256          # the longest line csrc/lfm_dft_any.hip serves
+_MAXR = 16             # the largest stage held in registers
+
+
+def _smooth_plans(n):
+    """Every way to write n as a product of at most three stages in 2.._MAXR, ascending within a plan."""
+    out = []
+    for a in range(2, _MAXR + 1):
+        if n == a:
+            out.append((a,))
+        if n % a:
+            continue
+        for b in range(a, _MAXR + 1):
+            if n // a == b:
+                out.append((a, b))
+            if (n // a) % b:
+                continue
+            c = n // a // b
+            if b <= c <= _MAXR:
+                out.append((a, b, c))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def dft_plan(n):
+    """The stages (r1, r2, r3) of the line transform of length n in csrc/lfm_dft_any.hip, product n, for 1 <= n <= 256; None otherwise.
+    The rule: if n is a product of at most three stages <= 16, the plan with the FEWEST stages, among those the SMALLEST SUM of stages,
+    among those the smallest first stage (then second); stages ascending, unused stages are 1 and stand in front: 125 = (5, 5, 5),
+    250 = (5, 5, 10), 256 = (1, 16, 16), 13 = (1, 1, 13).  Any other n <= 256 is m * p with ONE prime 17 <= p <= 251 and m <= 15:
+    (1, m, p), the direct length-p stage last (where the passes along w can use the half spectrum and real outputs)."""
+    n = int(n)
+    if n < 1 or n > MAX_ANY:
+        return None
+    if n == 1:
+        return (1, 1, 1)
+    plans = _smooth_plans(n)
+    if plans:
+        best = min(plans, key=lambda p: (len(p), sum(p), p))
+        return (1,) * (3 - len(best)) + best
+    p = max(f for f in range(2, n + 1) if n % f == 0 and all(f % d for d in range(2, int(f ** 0.5) + 1)))
+    m = n // p
+    assert p > _MAXR and m < _MAXR, (n, p, m)       # holds for every n <= 256 (tests/test_lfm_dft_any_cpu.py walks them)
+    return (1, m, p)
+
+
+@functools.lru_cache(maxsize=None)
+def _axis_plan(n):
+    """The plan the _any entry points get for an axis: the old L1 x L2 split where csrc/lfm_dft.hip serves the length, else dft_plan."""
+    code = int(lib().ocpg_lfm_dft_split(int(n)))
+    return (code >> 8, code & 255, 1) if code else dft_plan(n)
+
+
+def dft_any_supported(h, w):
+    return dft_plan(h) is not None and dft_plan(w) is not None
+
+
+def _twiddles_any(n, device):
+    """The table of a line transform of length n under _axis_plan(n) (include/ocpg_hip.h, ocpg_lfm_spectrum_fwd_any), formed in fp64:
+    float2 exp(-2 pi i m / n) [n]; the s-point DFT matrix of every stage 1 < s <= 16 in plan order; int32 [n], the slot of element k."""
+    from ....util.misc import memo
+
+    def make():
+        plan = _axis_plan(n)
+
+        def angles(idx, m):
+            a = idx.to(torch.float64) * (-2.0 * torch.pi / m)
+            return torch.stack([a.cos(), a.sin()], -1)
+        parts = [angles(torch.arange(n), n)]
+        for r in plan:
+            if 1 < r <= _MAXR:
+                k = torch.arange(r)
+                parts.append(angles((k[:, None] * k[None, :]).remainder(r).flatten(), r))
+        s0, s1, s2 = ([r for r in plan if r != 1] + [1, 1, 1])[:3]
+        k = torch.arange(n)
+        slot = ((k % s0) * s1 + (k // s0) % s1) * s2 + k // (s0 * s1)
+        return torch.cat([torch.cat(parts).float().flatten(), slot.to(torch.int32).view(torch.float32)]).contiguous().to(device)
+    return memo("lfm_tw_any", n, device, make)
+
+
+def _route(h, w):
+    """0: csrc/lfm_dft.hip serves the map; 1: csrc/lfm_dft_any.hip does; raises when neither."""
+    if dft_supported(h, w):
+        return 0
+    if not dft_any_supported(h, w):
+        raise RuntimeError(f"LFM transforms: a {h} x {w} map is served by neither csrc/lfm_dft.hip nor csrc/lfm_dft_any.hip")
+    return 1
+
+
+def _slab(length):
+    return 32 if length > 128 else 64          # channels per workgroup of a pass along an axis of this length (lfm_dft_any.hip)
+
+
 def _nhwc32(x):
     """[N, C, h, w] -> its channels-last memory as an fp32 [N, h, w, C] contiguous tensor (a view when it already is)."""
     v = x.permute(0, 2, 3, 1)
@@ -231,12 +327,17 @@ def _pair_cl(y):
 def _spectrum(x_nhwc, coef, high, norm, dtype):
     n, h, w, c = x_nhwc.shape
     dev = x_nhwc.device
+    any_ = _route(h, w)
     tmp = torch.empty((n, h, w // 2 + 1, c, 2), dtype=torch.float32, device=dev)
     pair = torch.empty((n, h, w, 2 * c), dtype=dtype, device=dev)
-    check(lib().ocpg_lfm_spectrum_fwd(x_nhwc.data_ptr(), coef.data_ptr() if coef is not None else None,
-                                      high.data_ptr() if high is not None else None, n, h, w, c, _twiddles(h, dev).data_ptr(),
-                                      _twiddles(w, dev).data_ptr(), float(norm), tmp.data_ptr(), pair.data_ptr(), _DT[dtype],
-                                      torch.cuda.current_stream().cuda_stream), "ocpg_lfm_spectrum_fwd")
+    args = (x_nhwc.data_ptr(), coef.data_ptr() if coef is not None else None, high.data_ptr() if high is not None else None, n, h, w, c)
+    if any_:
+        check(lib().ocpg_lfm_spectrum_fwd_any(*args, _twiddles_any(h, dev).data_ptr(), _twiddles_any(w, dev).data_ptr(), float(norm), tmp.data_ptr(),
+                                              pair.data_ptr(), _DT[dtype], *_axis_plan(h), *_axis_plan(w), torch.cuda.current_stream().cuda_stream),
+              "ocpg_lfm_spectrum_fwd_any")
+    else:
+        check(lib().ocpg_lfm_spectrum_fwd(*args, _twiddles(h, dev).data_ptr(), _twiddles(w, dev).data_ptr(), float(norm), tmp.data_ptr(),
+                                          pair.data_ptr(), _DT[dtype], torch.cuda.current_stream().cuda_stream), "ocpg_lfm_spectrum_fwd")
     return pair
 
 
@@ -244,20 +345,26 @@ def _inverse(pair, coef, high, z_saved, want_coef, norm, residual):
     n, h, w, c2 = pair.shape
     c = c2 // 2
     dev = pair.device
+    any_ = _route(h, w)
+    slab = _slab(h) if any_ else 64
     tmp = torch.empty((n, h, w // 2 + 1, c, 2), dtype=torch.float32, device=dev)
     out = torch.empty((n, h, w, c), dtype=torch.float32, device=dev)
-    part = torch.empty((n, (w // 2 + 1) * ((c + 63) // 64)), dtype=torch.float32, device=dev) if want_coef else None
-    check(lib().ocpg_lfm_spectrum_inv(pair.data_ptr(), _DT[pair.dtype], coef.data_ptr() if coef is not None else None,
-                                      high.data_ptr() if high is not None else None, z_saved.data_ptr() if want_coef else None,
-                                      part.data_ptr() if want_coef else None, n, h, w, c, _twiddles(h, dev).data_ptr(), _twiddles(w, dev).data_ptr(),
-                                      float(norm), tmp.data_ptr(), residual.data_ptr() if residual is not None else None, out.data_ptr(),
-                                      torch.cuda.current_stream().cuda_stream), "ocpg_lfm_spectrum_inv")
+    part = torch.empty((n, (w // 2 + 1) * ((c + slab - 1) // slab)), dtype=torch.float32, device=dev) if want_coef else None
+    args = (pair.data_ptr(), _DT[pair.dtype], coef.data_ptr() if coef is not None else None, high.data_ptr() if high is not None else None,
+            z_saved.data_ptr() if want_coef else None, part.data_ptr() if want_coef else None, n, h, w, c)
+    tail = (float(norm), tmp.data_ptr(), residual.data_ptr() if residual is not None else None, out.data_ptr())
+    if any_:
+        check(lib().ocpg_lfm_spectrum_inv_any(*args, _twiddles_any(h, dev).data_ptr(), _twiddles_any(w, dev).data_ptr(), *tail, *_axis_plan(h),
+                                              *_axis_plan(w), torch.cuda.current_stream().cuda_stream), "ocpg_lfm_spectrum_inv_any")
+    else:
+        check(lib().ocpg_lfm_spectrum_inv(*args, _twiddles(h, dev).data_ptr(), _twiddles(w, dev).data_ptr(), *tail,
+                                          torch.cuda.current_stream().cuda_stream), "ocpg_lfm_spectrum_inv")
     return out, part
 
 
 class LFMSpectrum(Function):
     """z = cat([Re, Im], 1)(fft2(x) * (1 - coef * high)) of a real map (models/modules.py:44-50) as a [N, 2C, h, w] tensor in
-    channels-last memory and the 1x1 convs' compute dtype: two passes of csrc/lfm_dft.hip.  Backward: the real part of the unnormalised
+    channels-last memory and the 1x1 convs' compute dtype: two passes of csrc/lfm_dft.hip (csrc/lfm_dft_any.hip for a map that one refuses).  Backward: the real part of the unnormalised
     inverse transform of gate * gz, and the gate coefficient's gradient from the saved z."""
 
     @staticmethod
