@@ -229,6 +229,26 @@ int ocpg_gemm_dgrad_bn_tile(long long M, int N, int K);
 int ocpg_gemm_dgrad_bn(const void* a, const void* w, const void* c, const void* mask, const float* scale, void* out, void* out_skip,
                        long long M, int N, int K, int dtype, int tile, void* stream);
 
+/* The encoder FFN's bias + ReLU + dropout passes as epilogues of the same tile code (bf16 only; tiles as above, every tile the same bits).
+ * Backward, linear2's input gradient with ocpg_bias_relu_dropout_bwd in its epilogue:
+ *   v[m,n] = sum_k a[m,k] w[k,n]                 a [M,K] the gradient at linear2's output, w = linear2.weight [K][N] as it lies
+ *   g      = mask[m,n] > 0 ? v * scale : 0       mask = the saved hidden map h (zero where ReLU or dropout zeroed it), scale = 1/(1-p)
+ *   out[m,n] = bf16(g)
+ *   colsum_part[t][n] = sum of g (fp32, before narrowing) over the valid rows of row tile t, t < ceil(M / tile rows (128, 64, 64)):
+ *                       plain stores, every element written exactly once, fixed order, no atomics (the caller sums the tiles: the bias gradient)
+ * Forward, linear1 with ocpg_bias_relu_dropout_fwd in its epilogue:
+ *   h[m,n] = bf16(max(sum_k x[m,k] w[n,k] + bias[n], 0) * keep)      w = linear1.weight [N][K] as it lies; keep = 0 or 1/(1-p), drawn as
+ *   ocpg_bias_relu_dropout_fwd draws it (counter (m N + n) / 4, offset + *rng_base): the same (seed, offset) gives the same mask; p = 0 draws nothing.
+ *   round_gemm != 0: h[m,n] = bf16(max(bf16(sum) + bias[n], 0) * keep), the arithmetic of the pair (a bf16 GEMM result, then the pass): the same h
+ *   wherever both GEMMs' fp32 sums round to the same bf16 value.  0 is one rounding closer to the exact result, but a pre-activation within a
+ *   bf16 spacing of zero can then fall on the other side of the ReLU than the pair puts it.
+ * Neither call allocates.  Declined exactly as ocpg_gemm_dgrad_bn declines (-2000 shape, -2001 alignment, -2002 dtype other than 1). */
+int ocpg_gemm_dgrad_mask(const void* a, const void* w, const void* mask, float scale, void* out, float* colsum_part, long long M, int N,
+                         int K, int dtype, int tile, void* stream);
+int ocpg_gemm_bias_relu_dropout_fwd(const void* x, const void* w, const void* bias, float p, unsigned long long seed,
+                                    unsigned long long offset, const unsigned long long* rng_base, void* h, long long M, int N, int K,
+                                    int dtype, int tile, int round_gemm, void* stream);
+
 /* Fused 3-D (shifted-)window attention of Video-Swin -- replaces WindowAttention3D.forward's score / bias / mask /
  * softmax / PV chain (models/video_swin_transformer.py:138-169) and the shift-mask tensor of compute_mask (:316-329).
  *   qkv    [BW, N, 3, H, head_dim]   output of the qkv Linear (BW = batch * windows), head_dim must be 32

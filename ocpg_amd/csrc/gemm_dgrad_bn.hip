@@ -17,6 +17,11 @@
 // (8 consecutive k of one n) are read with gfx950's transposing ds_read_b64_tr_b16 (conv3x3_mfma's BTR path).  The accumulators leave
 // through LDS so that every thread handles 8 consecutive columns of one row: 16-byte loads of C and the mask, 16-byte stores.  Every
 // output element is one fp32 chain over k in ascending order, whatever the tile: deterministic, and the same bits for every tile.
+//
+// The same tile code also serves the encoder FFN of the transformer (MODE below, bf16): linear2's input gradient with the bias + ReLU +
+// dropout backward and the bias gradient's partial column sums in its epilogue (ocpg_gemm_dgrad_mask), and linear1 with bias + ReLU +
+// dropout in its epilogue (ocpg_gemm_bias_relu_dropout_fwd; the weight [N][K] as it lies, plain fragment reads).  The MODE_BN
+// instantiations are the kernels they were before the modes existed.
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
@@ -24,6 +29,7 @@
 
 #include "../../include/ocpg_hip.h"
 #include "h16_elem.h"
+#include "philox.h"
 
 namespace {
 
@@ -84,6 +90,27 @@ struct EpiT {
 };
 using Epi = EpiT<__hip_bfloat16>;
 
+// What the tile code computes.  BN: the 1x1 input gradient above (epilogue EpiT).  The two FFN modes (FfnT, encoder FFN of the transformer):
+//   FFN_MASK  out = bf16(v * scale * [mask > 0]) with a SCALAR scale, plus the partial column sums of that value (before narrowing) over
+//             the row tile: linear2's input gradient with the bias + ReLU + dropout backward of the hidden map in its epilogue;
+//   FFN_FWD   B = linear1's weight [N][K] as it lies (k contiguous: plain fragment reads), out = bf16(max(v + bias[n], 0) * keep),
+//             keep drawn as fused_ln.hip's brd_fwd draws it (counter = element index / 4, offset0 + *rng_base).  round_v: v is rounded
+//             to bf16 before the bias is added, which is the arithmetic of the pair it replaces (a bf16 GEMM result, then brd_fwd):
+//             the same h wherever the two GEMMs' fp32 sums round to the same bf16 value.
+constexpr int MODE_BN = 0, MODE_FFN_MASK = 1, MODE_FFN_FWD = 2;
+template <typename T>
+struct FfnT {
+  const T* mask;               // FFN_MASK: the saved hidden map h
+  const T* bias;               // FFN_FWD
+  T* out;
+  float* colsum;               // FFN_MASK: [mtiles][N], every element stored once
+  float scale;                 // 1 / (1 - p)
+  uint32_t thr;                // FFN_FWD: p * 2^32 (0: nothing is drawn)
+  uint64_t seed, offset0;
+  const uint64_t* rng_base;
+  int round_v;                 // FFN_FWD: round v to bf16 before the bias (the pair's arithmetic)
+};
+
 // C and mask of 8 consecutive columns, loaded ahead of the arithmetic (all of a thread's loads in flight at once: the epilogue is the
 // memory-bound part of the short-K sites)
 struct In8 { uint4 c, y; };
@@ -119,20 +146,23 @@ __device__ __forceinline__ void epilogue8(const EpiT<typename E::T>& e, long lon
 }
 
 // grid: mtiles * ntiles workgroups (1-D)
-template <typename E, int TM, int TN>
+template <typename E, int TM, int TN, int MODE = MODE_BN>
 __device__ __forceinline__ void gemm_dgrad_bn_body(const typename E::T* __restrict__ a, const typename E::T* __restrict__ w,
-                                                   const EpiT<typename E::T>& e, long long M, int N, int K, int mtiles, int ntiles) {
+                                                   const EpiT<typename E::T>& e, long long M, int N, int K, int mtiles, int ntiles,
+                                                   const FfnT<typename E::T>& f = FfnT<typename E::T>{}) {
   using T = typename E::T;
+  constexpr bool BNK = MODE == MODE_FFN_FWD;                // B lies [N][K]: staged [n][k] like A, read without the transposing loads
   constexpr int BLD = TN + 8;          // B image [k][n]: rows 16-B aligned, 4 banks apart
   constexpr int SLD = TN + 4;          // fp32 accumulator image [m][n] for the epilogue
   constexpr int WM = TM / 2, WN = TN / 2, IM = WM / 32, JN = WN / 32;     // wave tile and its 32x32 accumulators
   constexpr int A_L = TM * BK / 8 / NT;                    // 16-B loads per thread and K step
-  constexpr int BSEG = TN / 8, BROWS = NT / BSEG, B_L = BK / BROWS;
-  constexpr int SMEM_SHORTS = 2 * (TM * ALD + BK * BLD);
+  constexpr int BSEG = TN / 8, BROWS = NT / BSEG, B_L = BNK ? TN * BK / 8 / NT : BK / BROWS;
+  constexpr int B_SHORTS = BNK ? TN * ALD : BK * BLD;
+  constexpr int SMEM_SHORTS = 2 * (TM * ALD + B_SHORTS);
   static_assert(TM * SLD * 2 <= SMEM_SHORTS, "the fp32 tile fits the staging buffers");
   __shared__ __attribute__((aligned(16))) short smem[SMEM_SHORTS];
   short (*As)[TM * ALD] = reinterpret_cast<short (*)[TM * ALD]>(smem);
-  short (*Bs)[BK * BLD] = reinterpret_cast<short (*)[BK * BLD]>(smem + 2 * TM * ALD);
+  short (*Bs)[B_SHORTS] = reinterpret_cast<short (*)[B_SHORTS]>(smem + 2 * TM * ALD);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave & 1, wn = wave >> 1;                 // wave tile: rows wm * WM .., columns wn * WN ..
   // consecutive workgroups land on different XCDs (round robin over 8): give each XCD a contiguous run of tiles, so the column tiles of
@@ -153,15 +183,16 @@ __device__ __forceinline__ void gemm_dgrad_bn_body(const typename E::T* __restri
     const long long r = min(m0 + arow + 32 * i, M - 1);
     ap[i] = a + r * K + aseg * 8;
   }
-  const T* wp = w + (long long)kr * N + n0 + bseg * 8;
-  const long long wstep = (long long)BROWS * N;            // B rows between a thread's consecutive loads
+  // ([N][K] weight: row n0 + arow + 32 i, segment aseg, as A; N % TN == 0, no row to clamp)
+  const T* wp = BNK ? w + (long long)(n0 + arow) * K + aseg * 8 : w + (long long)kr * N + n0 + bseg * 8;
+  const long long wstep = BNK ? 32ll * K : (long long)BROWS * N;     // B rows between a thread's consecutive loads
 
   // register sets are native vectors: with HIP's uint4 (a class) the two sets lived in scratch
   auto fetch = [&](u32x4 (&Ra)[A_L], u32x4 (&Rb)[B_L], int s) __attribute__((always_inline)) {   // K step s, clamped (valid memory)
     const int ks = min(s, ksteps - 1);
 #pragma unroll
     for (int i = 0; i < A_L; ++i) Ra[i] = *reinterpret_cast<const u32x4*>(ap[i] + ks * BK);
-    const T* wk = wp + (long long)ks * BK * N;
+    const T* wk = BNK ? wp + ks * BK : wp + (long long)ks * BK * N;
 #pragma unroll
     for (int i = 0; i < B_L; ++i) Rb[i] = *reinterpret_cast<const u32x4*>(wk + i * wstep);
   };
@@ -169,7 +200,10 @@ __device__ __forceinline__ void gemm_dgrad_bn_body(const typename E::T* __restri
 #pragma unroll
     for (int i = 0; i < A_L; ++i) *reinterpret_cast<u32x4*>(&As[buf][(arow + 32 * i) * ALD + aseg * 8]) = Ra[i];
 #pragma unroll
-    for (int i = 0; i < B_L; ++i) *reinterpret_cast<u32x4*>(&Bs[buf][(kr + BROWS * i) * BLD + bseg * 8]) = Rb[i];
+    for (int i = 0; i < B_L; ++i) {
+      if constexpr (BNK) *reinterpret_cast<u32x4*>(&Bs[buf][(arow + 32 * i) * ALD + aseg * 8]) = Rb[i];
+      else *reinterpret_cast<u32x4*>(&Bs[buf][(kr + BROWS * i) * BLD + bseg * 8]) = Rb[i];
+    }
   };
 
   f32x16 acc[IM * JN];
@@ -197,7 +231,10 @@ __device__ __forceinline__ void gemm_dgrad_bn_body(const typename E::T* __restri
 #pragma unroll
       for (int i = 0; i < IM; ++i) af[i] = *reinterpret_cast<const bf16x8*>(&As[buf][(wm * WM + i * 32 + fr) * ALD + kk * 16 + fh * 8]);
 #pragma unroll
-      for (int j = 0; j < JN; ++j) bf[j] = btr(buf, kk * 16, wn * WN + j * 32);
+      for (int j = 0; j < JN; ++j) {
+        if constexpr (BNK) bf[j] = *reinterpret_cast<const bf16x8*>(&Bs[buf][(wn * WN + j * 32 + fr) * ALD + kk * 16 + fh * 8]);
+        else bf[j] = btr(buf, kk * 16, wn * WN + j * 32);
+      }
 #pragma unroll
       for (int i = 0; i < IM; ++i)
 #pragma unroll
@@ -211,6 +248,17 @@ __device__ __forceinline__ void gemm_dgrad_bn_body(const typename E::T* __restri
   u32x4 R0a[A_L], R0b[B_L], R1a[A_L], R1b[B_L];
   fetch(R0a, R0b, 0);
   fetch(R1a, R1b, 1);
+  // FFN_MASK: the tile's share of the mask (thread = row group tid / BSEG, 8 columns, as its epilogue below) is requested right behind
+  // the first two operand fetches (younger than both: no wait of the first K step covers it), so that this HBM read runs under the K loop
+  constexpr int NQM = MODE == MODE_FFN_MASK ? TM * TN / 8 / NT : 1;
+  u32x4 ymask[NQM];
+  if constexpr (MODE == MODE_FFN_MASK) {
+#pragma unroll
+    for (int q = 0; q < NQM; ++q) {
+      const long long grow = min(m0 + tid / BSEG + (NT / BSEG) * q, M - 1);        // rows past M re-read row M - 1 (never used)
+      ymask[q] = *reinterpret_cast<const u32x4*>(f.mask + grow * N + n0 + (tid % BSEG) * 8);
+    }
+  }
   park(0, R0a, R0b);
   __syncthreads();
   for (int s = 0; s < ksteps; s += 2) {                    // R1 holds step s + 1, R0 (step s, parked) takes step s + 2; then they swap
@@ -240,6 +288,71 @@ __device__ __forceinline__ void gemm_dgrad_bn_body(const typename E::T* __restri
   // ---- thread = (row, 8 consecutive columns), NQ of them per thread; every C / mask load is issued before the first store.  Rows past M
   // load nothing (at a ragged edge C is written in place by other threads: no thread reads an element it does not own)
   constexpr int NQ = TM * TN / 8 / NT;
+  if constexpr (MODE == MODE_FFN_MASK) {
+    // NT % BSEG == 0: a thread keeps its 8 columns for all its NQ rows (row group rg, rows rg + RG q) and sums them in ascending q
+    constexpr int RG = NT / BSEG;
+    const int rg = tid / BSEG, c8 = (tid % BSEG) * 8;
+    float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int row = rg + RG * q;
+      const long long grow = m0 + row;
+      if (grow >= M) continue;
+      const float4 x0 = *reinterpret_cast<const float4*>(&st[row * SLD + c8]), x1 = *reinterpret_cast<const float4*>(&st[row * SLD + c8 + 4]);
+      float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w}, yv[8];
+      E::unpack8(*reinterpret_cast<const uint4*>(&ymask[q]), yv);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        v[i] = yv[i] > 0.f ? v[i] * f.scale : 0.f;
+        cs[i] += v[i];
+      }
+      *reinterpret_cast<uint4*>(f.out + grow * N + n0 + c8) = E::pack8(v);
+    }
+    // the RG partial sums of a column through the (now free) tile image, added in ascending row group by one thread: a fixed order
+    static_assert(RG <= TM, "the partial sums fit the tile image");
+    __syncthreads();
+    *reinterpret_cast<float4*>(&st[rg * SLD + c8]) = make_float4(cs[0], cs[1], cs[2], cs[3]);
+    *reinterpret_cast<float4*>(&st[rg * SLD + c8 + 4]) = make_float4(cs[4], cs[5], cs[6], cs[7]);
+    __syncthreads();
+    if (tid < TN) {
+      float sum = 0.f;
+#pragma unroll
+      for (int g = 0; g < RG; ++g) sum += st[g * SLD + tid];
+      f.colsum[(long long)(t / ntiles) * N + n0 + tid] = sum;
+    }
+    return;
+  } else if constexpr (MODE == MODE_FFN_FWD) {
+    const uint64_t offset = f.offset0 + (f.rng_base ? *f.rng_base : 0ull);
+    const int c8 = (tid % BSEG) * 8;
+    float bv[8];
+    E::unpack8(*reinterpret_cast<const uint4*>(f.bias + n0 + c8), bv);
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int row = tid / BSEG + (NT / BSEG) * q;
+      const long long grow = m0 + row;
+      if (grow >= M) continue;
+      const float4 x0 = *reinterpret_cast<const float4*>(&st[row * SLD + c8]), x1 = *reinterpret_cast<const float4*>(&st[row * SLD + c8 + 4]);
+      float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+      if (f.round_v) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = __bfloat162float(__float2bfloat16(v[i]));
+      }
+      const long long off = grow * N + n0 + c8;
+      // fused_ln.hip's keep4 on counters off / 4 and off / 4 + 1, in scalars (its array form goes to scratch); p = 0 draws nothing
+      uint4 r0 = make_uint4(~0u, ~0u, ~0u, ~0u), r1 = r0;
+      if (f.thr != 0u) {
+        const uint2 key = make_uint2((uint32_t)f.seed, (uint32_t)(f.seed >> 32));
+        const uint64_t i4 = (uint64_t)off / 4;
+        r0 = ocpg_dev::philox(key, make_uint4((uint32_t)i4, (uint32_t)(i4 >> 32), (uint32_t)offset, (uint32_t)(offset >> 32)));
+        r1 = ocpg_dev::philox(key, make_uint4((uint32_t)(i4 + 1), (uint32_t)((i4 + 1) >> 32), (uint32_t)offset, (uint32_t)(offset >> 32)));
+      }
+      const uint32_t rr[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v[i] = fmaxf(v[i] + bv[i], 0.f) * (rr[i] >= f.thr ? f.scale : 0.f);
+      *reinterpret_cast<uint4*>(f.out + off) = E::pack8(v);
+    }
+    return;
+  }
   In8 in[NQ];
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
@@ -268,6 +381,12 @@ template <int TM, int TN>
 __global__ __launch_bounds__(NT) void gemm_dgrad_bn_f16(const __half* __restrict__ a, const __half* __restrict__ w, EpiT<__half> e,
                                                         long long M, int N, int K, int mtiles, int ntiles) {
   gemm_dgrad_bn_body<Fp16, TM, TN>(a, w, e, M, N, K, mtiles, ntiles);
+}
+
+template <int TM, int TN, int MODE>
+__global__ __launch_bounds__(NT) void gemm_ffn(const __hip_bfloat16* __restrict__ a, const __hip_bfloat16* __restrict__ w, FfnT<__hip_bfloat16> f,
+                                               long long M, int N, int K, int mtiles, int ntiles) {
+  gemm_dgrad_bn_body<Bf16, TM, TN, MODE>(a, w, Epi{}, M, N, K, mtiles, ntiles, f);
 }
 
 constexpr int TILE_M[3] = {128, 64, 64}, TILE_N[3] = {128, 128, 64};
@@ -317,4 +436,65 @@ extern "C" int ocpg_gemm_dgrad_bn(const void* a, const void* w, const void* c, c
   else gemm_dgrad_bn<64, 64><<<grid, block, 0, st>>>(ap, wp, e, M, N, K, mtiles, ntiles);
   const hipError_t err = hipGetLastError();
   return err == hipSuccess ? 0 : -(int)err;
+}
+
+namespace {
+
+template <int MODE>
+int launch_ffn(const void* a, const void* w, const FfnT<__hip_bfloat16>& f, long long M, int N, int K, int tile, hipStream_t st) {
+  const int mtiles = (int)((M + TILE_M[tile] - 1) / TILE_M[tile]), ntiles = N / TILE_N[tile];
+  const dim3 grid((unsigned)(mtiles * ntiles)), block(NT);
+  const __hip_bfloat16 *ap = (const __hip_bfloat16*)a, *wp = (const __hip_bfloat16*)w;
+  if (tile == 0) gemm_ffn<128, 128, MODE><<<grid, block, 0, st>>>(ap, wp, f, M, N, K, mtiles, ntiles);
+  else if (tile == 1) gemm_ffn<64, 128, MODE><<<grid, block, 0, st>>>(ap, wp, f, M, N, K, mtiles, ntiles);
+  else gemm_ffn<64, 64, MODE><<<grid, block, 0, st>>>(ap, wp, f, M, N, K, mtiles, ntiles);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? 0 : -(int)err;
+}
+
+}  // namespace
+
+extern "C" int ocpg_gemm_dgrad_mask(const void* a, const void* w, const void* mask, float scale, void* out, float* colsum_part, long long M, int N,
+                                    int K, int dtype, int tile, void* stream) {
+  if (dtype != 1) return DECLINE_DTYPE;
+  if (M < 0 || N <= 0 || K <= 0) return -1007;
+  if (tile < 0 || tile > 2) return -1011;
+  if (N % TILE_N[tile] != 0 || K % (2 * BK) != 0) return DECLINE_SHAPE;
+  if (!a) return -1001;
+  if (!w) return -1002;
+  if (!mask) return -1003;
+  if (!out) return -1006;
+  if (!colsum_part) return -1008;
+  const void* ptrs[] = {a, w, mask, out, colsum_part};
+  for (const void* p : ptrs)
+    if (!aligned16(p)) return DECLINE_ALIGN;
+  if (M == 0) return 0;
+  const FfnT<__hip_bfloat16> f{(const __hip_bfloat16*)mask, nullptr, (__hip_bfloat16*)out, colsum_part, scale, 0u, 0ull, 0ull, nullptr, 0};
+  return launch_ffn<MODE_FFN_MASK>(a, w, f, M, N, K, tile, (hipStream_t)stream);
+}
+
+extern "C" int ocpg_gemm_bias_relu_dropout_fwd(const void* x, const void* w, const void* bias, float p, unsigned long long seed,
+                                               unsigned long long offset, const unsigned long long* rng_base, void* h, long long M, int N, int K,
+                                               int dtype, int tile, int round_gemm, void* stream) {
+  if (dtype != 1) return DECLINE_DTYPE;
+  if (M < 0 || N <= 0 || K <= 0) return -1007;
+  if (!(p >= 0.f && p < 1.f)) return -1009;
+  if (tile < 0 || tile > 2) return -1011;
+  if (N % TILE_N[tile] != 0 || K % (2 * BK) != 0) return DECLINE_SHAPE;
+  if (!x) return -1001;
+  if (!w) return -1002;
+  if (!bias) return -1003;
+  if (!h) return -1006;
+  const void* ptrs[] = {x, w, bias, h};
+  for (const void* q : ptrs)
+    if (!aligned16(q)) return DECLINE_ALIGN;
+  if (M == 0) return 0;
+  uint32_t thr = 0u;                                       // fused_ln.hip's threshold(p)
+  if (p > 0.f) {
+    const double t = (double)p * 4294967296.0;
+    thr = t >= 4294967295.0 ? 4294967295u : (uint32_t)t;
+  }
+  const FfnT<__hip_bfloat16> f{nullptr, (const __hip_bfloat16*)bias, (__hip_bfloat16*)h, nullptr, 1.f / (1.f - p), thr, seed, offset,
+                               (const uint64_t*)rng_base, round_gemm != 0};
+  return launch_ffn<MODE_FFN_FWD>(x, w, f, M, N, K, tile, (hipStream_t)stream);
 }

@@ -65,12 +65,12 @@ def _both16(*ts):
     return ts[0].dtype in _H16 and all(t.dtype == ts[0].dtype for t in ts)
 
 
-def _offer_token(y, scale, skip, switch):
+def _offer_token(y, scale, skip, switch, what="conv + BN + ReLU"):
     """Producer's forward: y = relu(bn(...)) may have its frozen-BN + ReLU backward done by the input-gradient kernel of the consumer whose
     input IS y.  (The token identifies y by value, not by reference: ctx -> token -> y -> grad_fn -> ctx would be a cycle that keeps this
     forward's autograd graph alive until the garbage collector runs -- and a stale graph inside a later stream capture is the
     hipStreamEndCapture crash of DESIGN.md section 5.)"""
-    tok = {"y": _tensor_key(y), "scale": scale, "skip": skip, "switch": switch, "gz": None, "gskip": None, "ver": None}
+    tok = {"y": _tensor_key(y), "scale": scale, "skip": skip, "switch": switch, "what": what, "gz": None, "gskip": None, "ver": None}
     _PREMASK_TOKENS[y.data_ptr()] = tok
     return tok
 
@@ -95,7 +95,7 @@ def _take_token(tok, gy):
     gz, gskip, ver = tok["gz"], tok["gskip"], tok["ver"]
     tok["gz"] = tok["gskip"] = tok["ver"] = None
     if not (gy.data_ptr() == gz.data_ptr() and gy.shape == gz.shape and gy.stride() == gz.stride() and gy._version == ver):
-        raise RuntimeError(f"{tok['switch']}=1: the gradient of this conv + BN + ReLU output was produced with the BN + ReLU backward already "
+        raise RuntimeError(f"{tok['switch']}=1: the gradient of this {tok['what']} output was produced with that layer's backward already "
                            f"applied by its consumer's input-gradient kernel, but a different gradient arrived (a second consumer of the "
                            f"output, or a gradient hook); run with {tok['switch']}=0 for such a graph")
     return gz, gskip

@@ -23,6 +23,20 @@ from .gemm_func import mm
 # A/B switch, read once: the extra ports of the dropout+add+LayerNorm kernels (y + addend and a 16-bit copy of y forward, up to three
 # gradient addends and the Linear's bias-gradient partials backward) and the Linear + dropout/add/LN autograd node; 0 = the plain calls
 PORTS = os.environ.get("OCPG_FUSED_LN_PORTS", "1") != "0"
+# A/B switch, read once: the encoder FFN's bias + ReLU + dropout passes as epilogues of own MFMA GEMMs (csrc/gemm_dgrad_bn.hip, bf16, from
+# amp_cache.TOKEN_LINEAR_MIN_ROWS rows).  fwd: linear1 + ocpg_bias_relu_dropout_fwd = ocpg_gemm_bias_relu_dropout_fwd;  bwd: linear2's input
+# gradient (formed in LinearDropoutAddLayerNorm.backward) + ocpg_bias_relu_dropout_bwd = ocpg_gemm_dgrad_mask.  0 | fwd | bwd | 1 (both).
+# OCPG_FFN_FWD_EXACT (default 0): 1 = the fused forward adds the bias BEFORE the GEMM result is rounded to bf16 (one rounding fewer);
+# 0 = it rounds first, as the pair does.  The exact form decides ReLUs of pre-activations within a bf16 spacing of zero the other way than
+# the pair, which moves the step's outputs by more than a rounding, so it is opt-in.
+_FFN_FUSED = os.environ.get("OCPG_FFN_FUSED", "1")
+FFN_FWD_EXACT = os.environ.get("OCPG_FFN_FWD_EXACT", "0") != "0"
+if _FFN_FUSED not in ("0", "fwd", "bwd", "1"):
+    raise RuntimeError(f"OCPG_FFN_FUSED={_FFN_FUSED}: expected 0, fwd, bwd or 1")
+FFN_FUSED_FWD, FFN_FUSED_BWD = _FFN_FUSED in ("1", "fwd"), _FFN_FUSED in ("1", "bwd")
+FFN_TILE = 0                # 128 x 128, the fastest tile at the encoder's shapes (tools/bench_ffn_fused.py)
+FFN_TILE_ROWS = (128, 64, 64)       # rows of a workgroup tile (csrc/gemm_dgrad_bn.hip TILE_M): one row of partial column sums per row tile
+_FFN_DECLINED = (-2000, -2001, -2002)       # shape / alignment / dtype the fused symbols do not serve: the caller keeps the pair
 _calls = [0]
 _active = [None]            # the GraphRng whose capture is in progress (at most one per process)
 
@@ -198,8 +212,12 @@ class LinearDropoutAddLayerNorm(Function):
     @staticmethod
     def forward(ctx, x2, w, b, res, gamma, beta, p, eps, rng, addend, lp_dtype):
         from ...amp_cache import deferrable
+        from .conv_bn_func import _claim_token
         h = mm(x2, w, True, b)
         c = h.shape[-1]
+        # consumer: x2 IS a LinearBiasReluDropout output whose bias + ReLU + dropout backward this node's input-gradient GEMM can take over
+        ctx.claim = _claim_token(x2) if (FFN_FUSED_BWD and x2.dtype == torch.bfloat16 and w.dtype == x2.dtype and x2.is_contiguous()
+                                         and w.is_contiguous() and ctx.needs_input_grad[0]) else None
         res2 = res.reshape(-1, c).contiguous()
         ad2 = None if addend is None else addend.reshape(-1, c).contiguous()
         seed, offset, base = _unpack(rng)
@@ -226,24 +244,71 @@ class LinearDropoutAddLayerNorm(Function):
         gb = None
         if need_b:
             gb = defer_sum(gxsum, h.dtype) if (ctx.defer_b and h.dtype != torch.float32) else gxsum.sum(0).to(h.dtype)
-        gx = mm(gh, w) if ctx.needs_input_grad[0] else None
+        gx = None
+        if ctx.claim is not None and ctx.needs_input_grad[0]:
+            gx = _ffn_dgrad_mask(gh, w, x2, ctx.claim)
+        if gx is None and ctx.needs_input_grad[0]:
+            gx = mm(gh, w)
         gw = weight_grad(gh, x2, ctx.defer_w) if ctx.needs_input_grad[1] else None
         ga = gadd.reshape(ashape) if (gadd is not None and ctx.needs_input_grad[9]) else None
         return (gx, gw, gb, None if gres is None else gres.view(rshape), dgb[0], dgb[1], None, None, None, ga, None)
+
+
+def _ffn_rows_ok(r):
+    from ... import amp_cache
+    return r >= amp_cache.TOKEN_LINEAR_MIN_ROWS
+
+
+def _ffn_dgrad_mask(gh, w, h, tok):
+    """gx [R, N] = (gh [R, K] w [K, N]) * scale * [h > 0] by ocpg_gemm_dgrad_mask, the partial column sums parked on the producer's token;
+    None when the symbol declines (nothing written: the caller runs its GEMM and the producer its own backward pass)."""
+    r, k = gh.shape
+    n = w.shape[1]
+    if gh.dtype != h.dtype or not gh.is_contiguous() or tuple(w.shape) != (k, n) or tuple(h.shape) != (r, n) or not _ffn_rows_ok(r):
+        return None
+    L = lib()
+    gx = torch.empty_like(h)
+    tm = FFN_TILE_ROWS[FFN_TILE]
+    part = torch.empty(((r + tm - 1) // tm, n), dtype=torch.float32, device=h.device)      # one row of column sums per row tile
+    rc = L.ocpg_gemm_dgrad_mask(gh.data_ptr(), w.data_ptr(), h.data_ptr(), tok["scale"], gx.data_ptr(), part.data_ptr(), r, n, k, _DT[h.dtype],
+                                FFN_TILE, _st())
+    if rc in _FFN_DECLINED:
+        return None
+    check(rc, "ocpg_gemm_dgrad_mask")
+    from .conv_bn_func import _fill_token
+    _fill_token(tok, gx, part)
+    return gx
 
 
 class LinearBiasReluDropout(Function):
     @staticmethod
     def forward(ctx, x2, w, b, p, rng, splits):
         seed, offset, base = _unpack(rng)
-        h = mm(x2, w, True)
-        r, c = h.shape
-        check(lib().ocpg_bias_relu_dropout_fwd(h.data_ptr(), b.data_ptr(), r, c, float(p), seed, offset, base, _DT[h.dtype], h.data_ptr(), _st()),
-              "ocpg_bias_relu_dropout_fwd")
+        r, c = x2.shape[0], w.shape[0]
+        h = None
+        if (FFN_FUSED_FWD and x2.dtype == torch.bfloat16 and w.dtype == x2.dtype and b.dtype == x2.dtype and _ffn_rows_ok(r)
+                and x2.is_contiguous() and w.is_contiguous() and b.is_contiguous()):
+            h = torch.empty((r, c), dtype=x2.dtype, device=x2.device)
+            rc = lib().ocpg_gemm_bias_relu_dropout_fwd(x2.data_ptr(), w.data_ptr(), b.data_ptr(), float(p), seed, offset, base, h.data_ptr(), r, c,
+                                                       x2.shape[1], _DT[x2.dtype], FFN_TILE, 0 if FFN_FWD_EXACT else 1, _st())
+            if rc in _FFN_DECLINED:
+                h = None
+            else:
+                check(rc, "ocpg_gemm_bias_relu_dropout_fwd")
+        if h is None:
+            h = mm(x2, w, True)
+            check(lib().ocpg_bias_relu_dropout_fwd(h.data_ptr(), b.data_ptr(), r, c, float(p), seed, offset, base, _DT[h.dtype], h.data_ptr(), _st()),
+                  "ocpg_bias_relu_dropout_fwd")
         ctx.save_for_backward(x2, w, h)
         ctx.meta = (float(p), splits)
         from ...amp_cache import deferrable
         ctx.defer_w, ctx.defer_b = deferrable(w), deferrable(b) and b.dtype == h.dtype
+        # producer: the consumer whose input IS h (linear2 inside LinearDropoutAddLayerNorm) may apply this node's bias + ReLU + dropout
+        # backward in its input-gradient GEMM and leave the bias gradient's partial column sums on the token
+        ctx.offer = None
+        if FFN_FUSED_BWD and h.dtype == torch.bfloat16 and _ffn_rows_ok(r) and any(ctx.needs_input_grad[:3]):
+            from .conv_bn_func import _offer_token
+            ctx.offer = _offer_token(h, 1.0 / (1.0 - float(p)), False, "OCPG_FFN_FUSED", "Linear + bias + ReLU + dropout")
         return h
 
     @staticmethod
@@ -253,12 +318,17 @@ class LinearBiasReluDropout(Function):
         x2, w, h = ctx.saved_tensors
         p, splits = ctx.meta
         r, c = h.shape
-        gh = gh.to(h.dtype).contiguous()
-        ga = torch.empty_like(h)
-        slots = lib().ocpg_bias_relu_dropout_bwd_slots(r, c, _DT[h.dtype])
-        part = torch.empty((slots, c), dtype=torch.float32, device=h.device)
-        check(lib().ocpg_bias_relu_dropout_bwd(gh.data_ptr(), h.data_ptr(), r, c, p, _DT[h.dtype], ga.data_ptr(), part.data_ptr(), _st()),
-              "ocpg_bias_relu_dropout_bwd")
+        from .conv_bn_func import _take_token
+        fused = _take_token(ctx.offer, gh)
+        if fused is not None:       # linear2's input-gradient GEMM already applied this node's backward pass: gh IS ga
+            ga, part = fused
+        else:
+            gh = gh.to(h.dtype).contiguous()
+            ga = torch.empty_like(h)
+            slots = lib().ocpg_bias_relu_dropout_bwd_slots(r, c, _DT[h.dtype])
+            part = torch.empty((slots, c), dtype=torch.float32, device=h.device)
+            check(lib().ocpg_bias_relu_dropout_bwd(gh.data_ptr(), h.data_ptr(), r, c, p, _DT[h.dtype], ga.data_ptr(), part.data_ptr(), _st()),
+                  "ocpg_bias_relu_dropout_bwd")
         from ...amp_cache import defer_sum
         # the per-slot partial column sums: summed inside the fused gradient cast when the bias copy allows it (one launch less + no cast)
         dbias = defer_sum(part, h.dtype) if (ctx.defer_b and ctx.needs_input_grad[2] and h.dtype != torch.float32) else part.sum(0).to(h.dtype)
