@@ -371,6 +371,14 @@ int ocpg_conv3x3_mfma_dgrad_w_h16(const void* dy, const void* w, const void* mas
                                   int stride, void* dx, int dtype, void* stream);
 int ocpg_conv3x3_mfma_wgrad_h16(const void* gz, const void* x, int N, int H, int W, int Cin, int Cout, int stride, void* part, int dtype,
                                 void* stream);
+/* ocpg_conv3x3_mfma_wgrad(_h16) by the ring kernel (csrc/conv3x3_wgrad_ring_kernel.h): input rows roll through an LDS ring (a step fetches
+ * only the rows the ring does not hold yet), one barrier per step, 8 waves with the nine taps split 5 + 4.  Same arguments, checks in the
+ * same order, return codes, split (ocpg_conv3x3_mfma_wgrad_splits) and `part` layout as the twin, and every element of `part` bit-identical
+ * to the twin's (each accumulator sees the same 16-pixel k steps in the same order).  Served: maps of one segment per output row
+ * (Wo <= 64 under stride 1, Wo <= 32 under stride 2); a wider map returns -2000 before any launch, `part` untouched: call the twin. */
+int ocpg_conv3x3_mfma_wgrad_ring(const void* gz, const void* x, int N, int H, int W, int Cin, int Cout, int stride, void* part, void* stream);
+int ocpg_conv3x3_mfma_wgrad_ring_h16(const void* gz, const void* x, int N, int H, int W, int Cin, int Cout, int stride, void* part, int dtype,
+                                     void* stream);
 /* ocpg_conv3x3_mfma_dgrad_w(_h16) for stride 2 in parity-class tiles: a 64-row tile holds input pixels of one class (y & 1, x & 1) and walks
  * only the taps that reach it (4 for odd/odd, 2 for the mixed classes, 1 for even/even: 9 taps per 4 pixels, where the nine-tap symbols
  * walk 36 and multiply zero rows for 27 of them).  Same arguments, checks and return codes as the nine-tap twin; stride != 2 returns -2000.

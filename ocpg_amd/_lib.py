@@ -116,6 +116,8 @@ CENSUS = {"on": False, "calls": {}}
 # a symbol that is another ROW ORDER of a kernel (same arguments, bit-identical result) is also counted as the symbol it stands in for:
 # the census answers "which kernel family served this module", and that answer does not change with the row order
 CENSUS_ALSO = {"ocpg_conv3x3_mfma_dgrad_w_s2": "ocpg_conv3x3_mfma_dgrad_w", "ocpg_conv3x3_mfma_dgrad_w_s2_h16": "ocpg_conv3x3_mfma_dgrad_w_h16",
+               # the ring form of the 3x3 weight gradient (csrc/conv3x3_wgrad_ring_kernel.h): same arguments, bit-identical partial sums
+               "ocpg_conv3x3_mfma_wgrad_ring": "ocpg_conv3x3_mfma_wgrad", "ocpg_conv3x3_mfma_wgrad_ring_h16": "ocpg_conv3x3_mfma_wgrad_h16",
                # the same dropout+add+LayerNorm kernels with more ports (csrc/fused_ln.hip)
                "ocpg_dropout_add_ln_fwd_ex": "ocpg_dropout_add_ln_fwd", "ocpg_dropout_add_ln_bwd_ex": "ocpg_dropout_add_ln_bwd"}
 

@@ -62,6 +62,22 @@ struct WG {
 
 inline int seg_of(int stride) { return stride == 1 ? 64 : 32; }
 
+// ---- the ring kernel (conv3x3_wgrad_ring_kernel.h): rolling input rows, one barrier per step, 8 waves with the taps split 5 + 4
+constexpr int NTR = 512;
+template <int V>
+struct IC { static constexpr int value = V; };
+
+#define WGRAD_RING_KERNEL conv3x3_wgrad_ring
+#define WGRAD_ELEM Bf16
+#include "conv3x3_wgrad_ring_kernel.h"
+#undef WGRAD_RING_KERNEL
+#undef WGRAD_ELEM
+#define WGRAD_RING_KERNEL conv3x3_wgrad_ring_f16
+#define WGRAD_ELEM Fp16
+#include "conv3x3_wgrad_ring_kernel.h"
+#undef WGRAD_RING_KERNEL
+#undef WGRAD_ELEM
+
 }  // namespace
 
 extern "C" {
@@ -112,6 +128,47 @@ int ocpg_conv3x3_mfma_wgrad_h16(const void* gz, const void* x, int N, int H, int
 
 int ocpg_conv3x3_mfma_wgrad(const void* gz, const void* x, int N, int H, int W, int Cin, int Cout, int stride, void* part, void* stream) {
   return ocpg_conv3x3_mfma_wgrad_h16(gz, x, N, H, W, Cin, Cout, stride, part, 1, stream);
+}
+
+/* The ring kernel on the same operands: same validation order, return codes, `part` layout and split as ocpg_conv3x3_mfma_wgrad_h16, and
+ * bit-identical partial sums.  It serves maps of one segment per output row (Wo <= 64 under stride 1, <= 32 under stride 2); a wider map
+ * is declined with -2000 before any launch, and the caller runs the kernel above. */
+int ocpg_conv3x3_mfma_wgrad_ring_h16(const void* gz, const void* x, int N, int H, int W, int Cin, int Cout, int stride, void* part, int dtype,
+                                     void* stream) {
+  if (dtype != 1 && dtype != 2) return -1010;
+  if (N < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return -1003;
+  if ((stride != 1 && stride != 2) || Cin % 8 != 0 || Cout % 8 != 0) return -2000;
+  if ((W - 1) / stride + 1 > seg_of(stride)) return -2000;
+  if ((long long)W * Cin > 0x7fffffffLL || (long long)W * Cout > 0x7fffffffLL) return -2000;      // offsets inside a map row are ints
+  if (N == 0) return 0;
+  if (!gz) return -1001;
+  if (!x) return -1002;
+  if (!part) return -1009;
+  WG g;
+  g.N = N; g.H = H; g.W = W; g.Ho = (H - 1) / stride + 1; g.Wo = (W - 1) / stride + 1; g.Cin = Cin; g.Cout = Cout; g.stride = stride;
+  g.seg = seg_of(stride);
+  g.xw = (g.seg - 1) * stride + 3;
+  const int splits = ocpg_conv3x3_mfma_wgrad_splits(N, H, W, Cin, Cout, stride);
+  const long long rows = (long long)N * g.Ho;
+  g.rows_per_split = (int)((rows + splits - 1) / splits);
+  const dim3 grid((unsigned)((Cout + TM - 1) / TM), (unsigned)((Cin + TN - 1) / TN), (unsigned)splits);
+  const hipStream_t st = (hipStream_t)stream;
+  const int ks = (g.Wo + 15) / 16;      // k steps per output row: 1..4 under stride 1, 1..2 under stride 2
+#define RING(S_, SEG_, KS_)                                                                                                  \
+  if (dtype == 2) conv3x3_wgrad_ring_f16<S_, SEG_, KS_><<<grid, NTR, 0, st>>>((const __half*)gz, (const __half*)x, g, (__half*)part); \
+  else conv3x3_wgrad_ring<S_, SEG_, KS_><<<grid, NTR, 0, st>>>((const __hip_bfloat16*)gz, (const __hip_bfloat16*)x, g, (__hip_bfloat16*)part)
+  if (stride == 1) {
+    if (ks == 1) { RING(1, 64, 1); } else if (ks == 2) { RING(1, 64, 2); } else if (ks == 3) { RING(1, 64, 3); } else { RING(1, 64, 4); }
+  } else {
+    if (ks == 1) { RING(2, 32, 1); } else { RING(2, 32, 2); }
+  }
+#undef RING
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : -(int)e;
+}
+
+int ocpg_conv3x3_mfma_wgrad_ring(const void* gz, const void* x, int N, int H, int W, int Cin, int Cout, int stride, void* part, void* stream) {
+  return ocpg_conv3x3_mfma_wgrad_ring_h16(gz, x, N, H, W, Cin, Cout, stride, part, 1, stream);
 }
 
 }  // extern "C"

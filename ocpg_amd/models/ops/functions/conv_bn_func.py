@@ -379,6 +379,7 @@ def eligible3x3_mfma(x, conv):
 
 BODY_SPLITK = os.environ.get("OCPG_CONV3X3_SPLITK", "0") != "0"     # opt-in (-1 = where the tile grid is small, n = force n): split-K forward / input gradient of the body's 3x3 convs; measured +0.45 ms per step at 2 clips, neutral at 1 (r4)
 WGRAD_OWN = os.environ.get("OCPG_WGRAD_OWN", "1") != "0"     # A/B switch: conv3x3_mfma's weight gradient by csrc/conv3x3_wgrad.hip (0 = im2col + row-split GEMM)
+WGRAD_RING = os.environ.get("OCPG_WGRAD_RING", "1") != "0"     # A/B switch: the weight gradient by the ring kernel (csrc/conv3x3_wgrad_ring_kernel.h) where it serves the shape (one segment per output row; bit-identical partial sums), else the kernel above; measured -0.34 ms per step
 DGRAD_OWN_WEIGHT = os.environ.get("OCPG_DGRAD_OWN_WEIGHT", "1") != "0"     # A/B switch: conv3x3_mfma's input gradient reads the weight untransposed
 DGRAD_S2_CLASSES = os.environ.get("OCPG_DGRAD_S2_CLASSES", "1") != "0"     # A/B switch: the stride-2 own-weight input gradient in parity-class tiles (only the taps that reach a pixel; bit-identical)
 _MFMA_MIN_C = int(os.environ.get("OCPG_MFMA_CONV3X3_MIN_C", "128"))     # 64 also serves layer1 (frozen: forward only), measured 0.08 ms/step SLOWER than MIOpen there (r4)
@@ -487,7 +488,14 @@ class Conv3x3MfmaBNAct(Function):
                     # straight from the two maps (csrc/conv3x3_wgrad.hip): no patch matrix, no library GEMM
                     sp = int(L.ocpg_conv3x3_mfma_wgrad_splits(n, h, wd, c, co, stride))
                     part = torch.empty((sp, co, k), dtype=y.dtype, device=y.device)
-                    if fp16:
+                    rc = -2000      # the ring kernel first where it is switched on; it declines (-2000, nothing launched) maps wider than a segment
+                    if WGRAD_RING and fp16:
+                        rc = L.ocpg_conv3x3_mfma_wgrad_ring_h16(gz.data_ptr(), x.data_ptr(), n, h, wd, c, co, stride, part.data_ptr(), 2, st)
+                    elif WGRAD_RING:
+                        rc = L.ocpg_conv3x3_mfma_wgrad_ring(gz.data_ptr(), x.data_ptr(), n, h, wd, c, co, stride, part.data_ptr(), st)
+                    if rc != -2000:
+                        check(rc, "ocpg_conv3x3_mfma_wgrad_ring_h16" if fp16 else "ocpg_conv3x3_mfma_wgrad_ring")
+                    elif fp16:
                         check(L.ocpg_conv3x3_mfma_wgrad_h16(gz.data_ptr(), x.data_ptr(), n, h, wd, c, co, stride, part.data_ptr(), 2, st),
                               "ocpg_conv3x3_mfma_wgrad_h16")
                     else:
