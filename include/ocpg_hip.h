@@ -1049,6 +1049,50 @@ int ocpg_attn_hd64_fwd_f32(const float* qkv, const void* attend, int attend_i64,
                            void* stream);
 int ocpg_bias_act_f32(const float* x, const float* bias, long long R, int C, int act, float* y, void* stream);
 
+/* COCO run-length encoding of binary masks on the device (csrc/mask_rle.hip): the counts and the compressed
+ * string of models/postprocessors.py: rle_counts / rle_encode (the dict pycocotools' `encode` returns), byte for byte.
+ *   Format        pixels in COLUMN-major order, k = x * H + y, N = H * W.  Runs alternate 0, 1, 0, ...; the first run is the zeros, of
+ *                 length 0 when pixel 0 is set; the last run ends at N.  The string emits count c[i] as x = c[i] - c[i-2] for i > 2
+ *                 (from the fourth count on) and as c[i] otherwise, cut into 5-bit groups, low first, as 2's complement; a group is
+ *                 the last one when the remaining value is 0 and bit 4 is clear, or -1 and bit 4 is set; other groups carry 0x20;
+ *                 every group is offset by 48.  1..7 characters per count.
+ *   Two steps, so the call is NOT capturable: the number of runs depends on the data.  Step 1 (one of the two pack entries) writes
+ *   the column-major bitmap and per-chunk tables into the workspace and n_trans [n_masks] int32, the transitions of each mask; the
+ *   caller reads n_trans back, allocates counts and calls step 2 (ocpg_mask_rle_encode) with the same workspace, n_masks and max_n.
+ *   workspace     device memory, 8-byte aligned; max_n >= every mask's H * W.  ocpg_mask_rle_query writes its size in bytes for
+ *                 (n_masks, max_n) to *workspace_bytes_host and the chunk size to *chunk_pixels_host (HOST memory, either may be
+ *                 NULL): a mask's order is cut into chunks of 4096 pixels, one workgroup each.  The query launches nothing; it
+ *                 takes the stream like every entry of the family and does not use it.  The kernels read no word of the workspace
+ *                 that they did not write in this call.
+ * ocpg_mask_rle_pack_u8: mask m is the row-major [H_m, W_m] byte plane at base + off[m] (off [n_masks] int64, device; no alignment
+ *   needed), non-zero = set (torch.bool storage is such a plane).  Geometry [n_masks, 2] int32 = H_m, W_m, passed twice: geom_host
+ *   (host memory, validated before any launch) and geom (device memory, read by the kernel and clamped to 1 <= H, H * W <= max_n
+ *   before it addresses anything).  Nothing outside a plane's H * W bytes is read.
+ * ocpg_mask_rle_pack_logits_f32: the arguments of ocpg_refmask_counts_f32: src [B, Q, hs, ws] fp32, up, geometry [B, 4] int32 =
+ *   crop_h, crop_w, out_h, out_w (host and device, clamped likewise).  Mask m = b * Q + q has size out_h[b] x out_w[b]; its pixels
+ *   are decided exactly as ocpg_mask_tail_f32 mode 1 decides them (p > thr), negated when invert = 1.  Nothing at the original
+ *   resolution is written but the bitmap words.
+ * ocpg_mask_rle_encode: run_start [n_masks] int64, passed twice (host: validated; device: read by the kernels and clamped into
+ *   0 .. counts_cap): mask m's counts are counts[run_start[m] .. + n_runs[m]), int32, n_runs[m] = n_trans[m] + 1 (int32, device);
+ *   its string is the n_bytes[m] (int64, device) characters at bytes + 7 * run_start[m]: bytes holds 7 * counts_cap.
+ *   n_trans_host: what step 1 wrote, read back.  Elements of counts and bytes outside a mask's runs / characters are not written.
+ * Integer arithmetic only, no atomics, no memset, plain vector stores, no workgroup waits for another: 2 launches per step (pack,
+ * per-mask totals; runs, strings).
+ * Return codes, all before any launch (nothing written): n_masks, B, Q, hs, ws, up, max_n, counts_cap or a geometry entry <= 0:
+ * -1006;  invert outside 0..1: -2601;  geom_host / geom / n_trans_host / run_start_host / run_start NULL: -2605;  crop_h > hs*up or
+ * crop_w > ws*up: -2602;  H*W (or max_n) >= 2^31: -2603;  H*W > max_n: -2604;  more than 65535 masks, hs*up or ws*up >= 2^31 (grid
+ * axes and index range): -1008;  n_trans_host negative, run starts overlapping, or counts_cap smaller than a mask's start + its
+ * n_trans + 1: -2607;  n_trans (pack) or counts / n_runs / bytes / n_bytes (encode) NULL: -1015;  workspace NULL or not 8-byte
+ * aligned: -2606;  base, off or src NULL: -1001. */
+int ocpg_mask_rle_query(int n_masks, long long max_n, long long* workspace_bytes_host, int* chunk_pixels_host, void* stream);
+int ocpg_mask_rle_pack_u8(const unsigned char* base, const long long* off, int n_masks, const int* geom_host, const int* geom,
+                          long long max_n, int* n_trans, void* workspace, void* stream);
+int ocpg_mask_rle_pack_logits_f32(const float* src, int B, int Q, int hs, int ws, int up, const int* geom_host, const int* geom,
+                                  long long max_n, float thr, int invert, int* n_trans, void* workspace, void* stream);
+int ocpg_mask_rle_encode(int n_masks, long long max_n, const int* n_trans_host, const long long* run_start_host,
+                         const long long* run_start, long long counts_cap, int* counts, int* n_runs, unsigned char* bytes,
+                         long long* n_bytes, void* workspace, void* stream);
+
 /* library / build identification: returns e.g. "ocpg_hip gfx950 r1" */
 const char* ocpg_hip_version(void);
 

@@ -177,7 +177,7 @@ def evaluate_referred_masks(model, data_loader, postprocessor, device, amp_dtype
 
 
 @torch.no_grad()
-def evaluate_a2d(model, data_loader, device, amp_dtype=None, gt=None, native=None, threshold=0.5):
+def evaluate_a2d(model, data_loader, device, amp_dtype=None, gt=None, native=None, threshold=0.5, dump=None):
     """The whole A2D-Sentences / JHMDB-Sentences evaluation (reference engine.py:126-194) from integer counts: per batch the model's
     forward and ONE refmask_counts call (models/ops/functions/refmask_func.py) straight from `pred_masks[:, 0]` -- every query's mask
     against the ground truth at the original resolution as (|P & G|, |P|, |G|), with the post-processor's chain (un-pad, bilinear
@@ -189,14 +189,21 @@ def evaluate_a2d(model, data_loader, device, amp_dtype=None, gt=None, native=Non
     path of the reference's `*_annotations_in_coco_format.json`, or the dict metrics.load_coco_gt makes of it) the mask and its `area`
     come from there, keyed by `image_id`.  Without an `image_id` a sample is numbered (rank, position).  native: as refmask_counts.
     With a process group scores and counts are gathered, so every rank returns the same dict; every rank enters the collective, also
-    one whose loader was empty."""
+    one whose loader was empty.
+
+    dump: a path.  Every batch then also makes ONE rle_from_logits call (models/ops/functions/mask_rle_func.py) on the same logits,
+    geometry and threshold: the run-length encoding of every query's mask.  The predictions are gathered over the ranks (every rank
+    enters that collective too) and rank 0 writes the list the reference hands to COCO.loadRes (engine.py:158-177) as JSON:
+    [{"image_id", "category_id": 1, "segmentation": {"size", "counts": <ascii str>}, "score"}], samples in loader order, queries in
+    the post-processor's order.  metrics.load_coco_results reads it back.  The returned metrics do not change."""
     from . import metrics
+    from .models.ops.functions.mask_rle_func import rle_from_logits
     from .models.ops.functions.refmask_func import refmask_counts
     from .util.misc import get_rank, targets_to
     if isinstance(gt, (str, bytes)) or hasattr(gt, "__fspath__"):
         gt = metrics.load_coco_gt(gt)
     model.eval()
-    rank, seen, pending = get_rank(), 0, []
+    rank, seen, pending, dumped = get_rank(), 0, [], []
     for samples, targets in data_loader:
         ids = [t["image_id"] if "image_id" in t else (rank, seen + i) for i, t in enumerate(targets)]
         ids = [i.item() if torch.is_tensor(i) else i for i in ids]
@@ -215,6 +222,11 @@ def evaluate_a2d(model, data_loader, device, amp_dtype=None, gt=None, native=Non
         masks = [m if m.dtype in (torch.bool, torch.uint8) else m != 0 for m in masks]
         counts = refmask_counts(outputs["pred_masks"][:, 0].float(), 1, crops, sizes, masks, threshold=threshold, invert=True, native=native)
         pending.append((ids, outputs["pred_logits"][:, 0, :, 0].float().sigmoid(), counts, areas))
+        if dump is not None:
+            dumped.append(rle_from_logits(outputs["pred_masks"][:, 0].float(), 1, crops, sizes, threshold=threshold, invert=True, native=native))
+    if dump is not None:
+        metrics.write_coco_results(dump, [(i, s.tolist(), r) for (ids, scores, _, _), rles in zip(pending, dumped)
+                                          for i, s, r in zip(ids, scores, rles)])
     acc = metrics.RefMaskAccumulator()
     for ids, scores, counts, areas in pending:                                            # the readbacks, after the last launch
         acc.add(ids, scores, counts, areas)

@@ -334,3 +334,44 @@ def load_coco_gt(path) -> Dict:
         mask = rle_decode(ann["segmentation"])
         out[ann["image_id"]] = (torch.from_numpy(mask), float(ann["area"]) if "area" in ann else float(mask.sum()))
     return out
+
+
+def write_coco_results(path, samples):
+    """samples: [(image_id, [score per query], [run-length dict per query])] of this rank -> the reference's prediction list
+    (engine.py:158-163) as JSON at `path`, written by rank 0 after a gather over the ranks, in rank order.  Every rank must call it,
+    also one without samples.  Returns the list on rank 0, None elsewhere."""
+    import json
+
+    import torch.distributed as dist
+    preds = []
+    for image_id, scores, rles in samples:
+        for s, m in zip(scores, rles):
+            counts = m["counts"]
+            preds.append({"image_id": image_id, "category_id": 1,                    # a dummy label, as the reference has it
+                          "segmentation": {"size": [int(v) for v in m["size"]], "counts": counts.decode("ascii") if isinstance(counts, bytes) else counts},
+                          "score": float(s)})
+    rank = 0
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, preds)
+        preds, rank = [p for part in parts for p in part], dist.get_rank()
+    if rank != 0:
+        return None
+    with open(path, "w") as f:
+        json.dump(preds, f)
+    return preds
+
+
+def load_coco_results(path) -> Dict:
+    """A prediction list as write_coco_results makes it -> {image_id: [(score, mask uint8 tensor [H0, W0])]}, the queries of an image
+    in the file's order; an image_id that JSON turned into a list comes back as a tuple."""
+    import json
+
+    from .models.postprocessors import rle_decode
+    with open(path) as f:
+        data = json.load(f)
+    out = {}
+    for p in data:
+        image_id = tuple(p["image_id"]) if isinstance(p["image_id"], list) else p["image_id"]
+        out.setdefault(image_id, []).append((float(p["score"]), torch.from_numpy(rle_decode(p["segmentation"]))))
+    return out

@@ -4,7 +4,10 @@ the masks as COCO run-length encodings for the A2D-Sentences / JHMDB-Sentences /
 The reference encodes with pycocotools (`mask_util.encode`); that library is not in this image, so `rle_encode` restates the public
 COCO format (column-major runs starting with a run of zeros, counts delta-coded against the count two places back from the fourth on,
 5 payload bits per ASCII character offset by 48).  It is checked by round trips and hand-derived strings, NOT against pycocotools:
-parity of the compressed string is unpinned."""
+parity of the compressed string is unpinned.
+
+For GPU tensors the post-processors encode on the device (models/ops/functions/mask_rle_func.py, csrc/mask_rle.hip): the same strings,
+byte for byte, without copying a plane to the host."""
 from typing import Dict, List
 
 import numpy as np
@@ -69,14 +72,26 @@ def rle_decode(rle: Dict) -> np.ndarray:
     return flat.reshape((h, w), order="F")
 
 
+def _rle_masks(planes, native):
+    """[q, H, W] bool planes -> their encodings.  native: None = on the device for GPU tensors; True = on the device or an error;
+    False = every plane copied to the host and walked there."""
+    if native is None:
+        native = planes.is_cuda
+    if not native:
+        return [rle_encode(q) for q in planes.cpu()]
+    from .ops.functions.mask_rle_func import rle_encode_masks
+    return rle_encode_masks(planes, native=True)
+
+
 class A2DSentencesPostProcess(nn.Module):
     """postprocessors.py:14-53: one annotated frame per sample (T = 1): per query the score, the mask un-padded to the augmented size,
     resized (bilinear) to the original size and binarised -- as `1 - (sigmoid > 0.5)`, the inversion the reference applies (:43) --
-    plus its run-length encoding."""
+    plus its run-length encoding.  native: where the encoding is made (_rle_masks)."""
 
-    def __init__(self, threshold=0.5):
+    def __init__(self, threshold=0.5, native=None):
         super().__init__()
         self.threshold = threshold
+        self.native = native
 
     @torch.no_grad()
     def forward(self, outputs, orig_target_sizes, max_target_sizes):
@@ -88,7 +103,7 @@ class A2DSentencesPostProcess(nn.Module):
             mh, mw = int(resized[0]), int(resized[1])
             m = F.interpolate(m[:, :mh, :mw].unsqueeze(1).float(), size=tuple(int(v) for v in orig.tolist()), mode="bilinear", align_corners=False)
             m = ~(m.sigmoid() > 0.5)                                                  # [q, 1, H, W] bool
-            predictions.append({"scores": s, "masks": m, "rle_masks": [rle_encode(q[0]) for q in m.cpu()]})
+            predictions.append({"scores": s, "masks": m, "rle_masks": _rle_masks(m[:, 0], self.native)})
         return predictions
 
 
@@ -109,11 +124,12 @@ class PostProcess(nn.Module):
 
 class PostProcessSegm(nn.Module):
     """postprocessors.py:96-143 (RefCOCO): masks re-ordered by descending query score, un-padded, resized to the original size,
-    `sigmoid > 0.5`, with their run-length encodings; called after PostProcess on its `results`."""
+    `sigmoid > 0.5`, with their run-length encodings; called after PostProcess on its `results`.  native: as _rle_masks."""
 
-    def __init__(self, threshold=0.5):
+    def __init__(self, threshold=0.5, native=None):
         super().__init__()
         self.threshold = threshold
+        self.native = native
 
     @torch.no_grad()
     def forward(self, results, outputs, orig_target_sizes, max_target_sizes):
@@ -126,15 +142,16 @@ class PostProcessSegm(nn.Module):
             m = m[order[i]][:, :int(resized[0]), :int(resized[1])].unsqueeze(1).float()
             m = F.interpolate(m, size=tuple(int(v) for v in orig.tolist()), mode="bilinear", align_corners=False).sigmoid() > 0.5
             results[i]["masks"] = m.to(torch.uint8)
-            results[i]["rle_masks"] = [rle_encode(x[0]) for x in m.cpu()]
+            results[i]["rle_masks"] = _rle_masks(m[:, 0], self.native)
         return results
 
 
 def build_postprocessors(args, dataset_name):
-    """postprocessors.py:145-152."""
+    """postprocessors.py:145-152; an optional `args.rle_native` says where the run-length strings are made (_rle_masks)."""
+    native = getattr(args, "rle_native", None)
     if dataset_name in ("a2d", "jhmdb"):
-        return A2DSentencesPostProcess(threshold=getattr(args, "threshold", 0.5))
+        return A2DSentencesPostProcess(threshold=getattr(args, "threshold", 0.5), native=native)
     post = {"bbox": PostProcess()}
     if getattr(args, "masks", False):
-        post["segm"] = PostProcessSegm(threshold=getattr(args, "threshold", 0.5))
+        post["segm"] = PostProcessSegm(threshold=getattr(args, "threshold", 0.5), native=native)
     return post
