@@ -665,6 +665,27 @@ int ocpg_lfm_spectrum_fwd_any(const float* x, const float* coef, const float* hi
 int ocpg_lfm_spectrum_inv_any(const void* pair, int pair_dt, const float* coef, const float* high, const void* z_saved, float* coef_part, int N, int H,
                               int W, int C, const void* tw_h, const void* tw_w, float norm, void* tmp, const float* residual, float* out, int h1, int h2,
                               int h3, int w1, int w2, int w3, void* stream);
+/* The same two transforms with a CHIRP-Z (Bluestein) line transform on one or both axes (csrc/lfm_dft_czt.hip): the arguments of the _any
+ * entries, in their order, plus cz_h / cz_w.  NULL: that axis runs its plan exactly as in the _any entries.  Not NULL: the axis is a chirp
+ * axis -- its length L must be 65..128 (prime or not), its plan must be given as (1, 1, L), and the pointer is its table; tw_h / tw_w of a
+ * chirp axis is not read but must still not be NULL.  A chirp line is X_k = c_k IFFT_256(FFT_256(a) B)_k with a_n = x_n c_n, c_n =
+ * exp(-i pi n^2 / L), B = FFT_256 of conj(c) wrapped around 256 (entry m and entry 256 - m hold conj(c_m), m < L, the rest zero); the
+ * inverse direction uses conj(c) and the FFT_256 of the wrapped c.  The table, formed in fp64 by the host, 896 float2:
+ *   [0, 128)    c_n for n < L, zero above;
+ *   [128, 384)  the forward B divided by 256, in the order the kernel reads it: entry 16 k1 + k2 holds B[k1 + 16 k2];
+ *   [384, 640)  the inverse B, the same way;
+ *   [640, 896)  exp(-2 pi i m / 256), m < 256.
+ * A pass along a chirp axis runs 32 channels per workgroup, so coef_part is [N, (W/2+1) * ceil(C / S)] with S = 32 when H is a chirp
+ * axis, else the _any entries' (H > 128 ? 32 : 64); tmp, pair, out, residual, z_saved as above.  Before any launch, writing nothing:
+ * the size codes of the _any entries; N == 0: 0; -2000 for a chirp axis outside 65..128, a chirp axis whose plan is not (1, 1, L) and
+ * whatever the _any entries refuse of the plan of the other axis; then their null-pointer / dtype codes in their order.  Two launches
+ * each, every size by value: capturable. */
+int ocpg_lfm_spectrum_fwd_czt(const float* x, const float* coef, const float* high, int N, int H, int W, int C, const void* tw_h, const void* tw_w,
+                              float norm, void* tmp, void* pair, int pair_dt, int h1, int h2, int h3, int w1, int w2, int w3, const void* cz_h,
+                              const void* cz_w, void* stream);
+int ocpg_lfm_spectrum_inv_czt(const void* pair, int pair_dt, const float* coef, const float* high, const void* z_saved, float* coef_part, int N, int H,
+                              int W, int C, const void* tw_h, const void* tw_w, float norm, void* tmp, const float* residual, float* out, int h1, int h2,
+                              int h3, int w1, int w2, int w3, const void* cz_h, const void* cz_w, void* stream);
 int ocpg_window_means3x3_fwd(const float* x, long long planes, int h, int w, int as_bf16, float* out, void* stream);
 int ocpg_window_means3x3_bwd(const float* gm, long long planes, int h, int w, float* dx, void* stream);
 /* The same on a channels-last map x [N, h, w, C] fp32 (round 4): part [N][ocpg_window_sums3x3_cl_bands(h)][C * 9] = window SUMS of a band of

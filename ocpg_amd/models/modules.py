@@ -13,8 +13,8 @@ from ..util.misc import memo
 from . import amp_cache, fallbacks
 import os
 
-from .ops.functions.spectral_func import (conv3x3_valid_spatial_mean, dft_any_supported, dft_plan, dft_supported, ifft2_real, lfm_inverse, lfm_spectrum,
-                                          pair_to_complex, spectral_gate, spectral_gate_cl)
+from .ops.functions.spectral_func import (CZT_MAX, CZT_MIN, conv3x3_valid_spatial_mean, dft_any_supported, dft_plan, dft_supported, ifft2_real, lfm_inverse,
+                                          lfm_spectrum, pair_to_complex, spectral_gate, spectral_gate_cl)
 
 FUSED_GATE = True       # A/B switch: fused spectral gate kernel
 GATE_NHWC = True        # A/B switch: gate output / inverse-FFT input in channels-last memory (1x1 convs as GEMMs, no casts / layout copies)
@@ -35,6 +35,53 @@ def dft_any_default(length):
     if plan is None:
         return False
     return max(plan) <= 16 or (max(plan) <= DFT_ANY_MAX_PRIME and length <= 128)
+
+
+# OCPG_LFM_DFT_CZT (default 1): a PRIME axis length p with DFT_CZT_MIN_PRIME <= p <= 127 runs the chirp-z line transform of csrc/lfm_dft_czt.hip
+# (the other axis: one the kernels above take by default, or a chirp axis itself); 0 restores the routing without it exactly, counted fallbacks
+# included; "force" sends every prime 67..127 to the chirp axis.  DFT_CZT_MIN_PRIME: the smallest prime from which the chirp route beat both the
+# library route and the direct stage on both axes, at that prime and every larger one (measured, DESIGN 4.8y: profiles/lfm_dft_czt_ab.jsonl);
+# None: no prime did, and the kernels stay behind "force".
+_CZT_ENV = os.environ.get("OCPG_LFM_DFT_CZT", "1")
+DFT_CZT = _CZT_ENV != "0"
+DFT_CZT_FORCE = _CZT_ENV == "force"
+DFT_CZT_MIN_PRIME = 67
+_CZT_FORCE_MIN = 67
+
+
+def _is_prime(v):
+    return v >= 2 and all(v % d for d in range(2, int(v ** 0.5) + 1))
+
+
+def dft_czt_axis(length):
+    """Is a line of this length a chirp axis under the switches as they stand?"""
+    if not DFT_CZT or not (CZT_MIN <= length <= min(CZT_MAX, 127)) or not _is_prime(length):
+        return False
+    lo = _CZT_FORCE_MIN if DFT_CZT_FORCE else DFT_CZT_MIN_PRIME
+    return lo is not None and length >= lo
+
+
+def _czt_range():
+    lo = _CZT_FORCE_MIN if DFT_CZT_FORCE else DFT_CZT_MIN_PRIME
+    return f"{lo}..127" if DFT_CZT and lo is not None else "(none: the chirp route is off)"
+
+
+def dft_route(h, w):
+    """Who runs both transforms of an h x w map, and the chirp axes (h, w): "old" csrc/lfm_dft.hip, "any" csrc/lfm_dft_any.hip, "czt"
+    csrc/lfm_dft_czt.hip, "library" rocFFT between transposing copies (a counted fallback when DFT_ANY is on).  Pure: reads the switches only."""
+    none = (False, False)
+    if not DFT_CL:
+        return "library", none
+    if dft_supported(h, w):
+        return "old", none
+    if not DFT_ANY:
+        return "library", none
+    axes = (dft_czt_axis(h), dft_czt_axis(w))
+    if any(axes) and all(on or dft_any_default(length) for on, length in zip(axes, (h, w))):
+        return "czt", axes
+    if dft_any_supported(h, w) and dft_any_default(h) and dft_any_default(w):
+        return "any", none
+    return "library", none
 
 
 LAPLACE_MEAN = True   # A/B switch: mean(laplace(x)) as nine window means + one small matrix product (no convolution)
@@ -89,16 +136,15 @@ class LFMResizeAdaptive(nn.Module):
             high._ocpg_key = key
         if x.is_cuda and FUSED_GATE and GATE_NHWC and c % 4 == 0:
             dt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else torch.float32
-            own = DFT_CL and dft_supported(h, w)
-            if not own and DFT_CL and DFT_ANY:
-                own = dft_any_supported(h, w) and dft_any_default(h) and dft_any_default(w)
-                if not own:         # the library route, counted (and an error under OCPG_STRICT_HIP=1); silent only with the switch off
-                    fallbacks.note("LFM", f"no own Fourier transform for a {h} x {w} map by default (a length above 256, a prime factor above "
-                                          f"{DFT_ANY_MAX_PRIME}, or one above 16 in a length above 128)", x)
-            if own:
-                z = lfm_spectrum(x, coef.float().reshape(b), high.reshape(h, w), dt)      # fft2 + gate + [Re || Im], channels-last
+            route, czt = dft_route(h, w)
+            if route == "library" and DFT_CL and DFT_ANY:
+                # counted (and an error under OCPG_STRICT_HIP=1); silent only with the switch off
+                fallbacks.note("LFM", f"no own Fourier transform for a {h} x {w} map by default (a length above 256, a prime factor above "
+                                      f"{DFT_ANY_MAX_PRIME} that is not a chirp-axis prime {_czt_range()}, or one above 16 in a length above 128)", x)
+            if route != "library":
+                z = lfm_spectrum(x, coef.float().reshape(b), high.reshape(h, w), dt, czt)      # fft2 + gate + [Re || Im], channels-last
                 y = self.conv2(F.relu(self.conv1(z)))
-                return lfm_inverse(y, x), high                                          # x + ifft2(.).real
+                return lfm_inverse(y, x, czt), high                                          # x + ifft2(.).real
             z = spectral_gate_cl(torch.fft.fft2(x), coef.float().reshape(b), high.reshape(h, w), dt)
             y = self.conv2(F.relu(self.conv1(z)))                   # channels-last in, channels-last out: two GEMMs
             y = ifft2_real(pair_to_complex(y), h, w)              # = torch.fft.ifft2(..., s=(h, w)).real, real-to-complex backward

@@ -1,6 +1,8 @@
 """Autograd binding of csrc/spectral.hip: the LFM block's spectral gate as one pass each way; of csrc/lfm_dft.hip and
-csrc/lfm_dft_any.hip: both Fourier transforms on the channels-last map, and the plan of every line length up to 256."""
+csrc/lfm_dft_any.hip: both Fourier transforms on the channels-last map, and the plan of every line length up to 256; of
+csrc/lfm_dft_czt.hip: the same with a chirp-z line transform on one or both axes."""
 import functools
+import os
 
 import torch
 from torch.autograd import Function
@@ -296,6 +298,39 @@ def _twiddles_any(n, device):
     return memo("lfm_tw_any", n, device, make)
 
 
+# ---- a chirp-z (Bluestein) line transform for any length 65..128 (csrc/lfm_dft_czt.hip) -------------------------------------------------
+CZT_MIN, CZT_MAX, CZT_M = 65, 128, 256      # the chirp lengths and the length of the cyclic convolution that serves them
+# channels per workgroup of a pass along a chirp axis (64 only in a diagnostic build of csrc/lfm_dft_czt.hip with -DOCPG_CZT_CHW=64)
+CZT_SLAB = 64 if "-DOCPG_CZT_CHW=64" in os.environ.get("OCPG_HIPCC_FLAGS", "").split() else 32
+
+
+def _twiddles_czt(n, device):
+    """The table of a chirp axis of length n (include/ocpg_hip.h, ocpg_lfm_spectrum_fwd_czt), formed in fp64: float2 [896] = the chirp
+    c_m = exp(-i pi m^2 / n) [128, zero from n on]; the forward B = FFT_256(wrapped conj(c)) / 256 and the inverse B = FFT_256(wrapped c) /
+    256, both [256] with entry 16 k1 + k2 holding B[k1 + 16 k2]; exp(-2 pi i m / 256) [256].  The chirp's angle is reduced as m^2 mod 2n
+    in integers first."""
+    from ....util.misc import memo
+
+    def make():
+        assert CZT_MIN <= n <= CZT_MAX, n
+        m = torch.arange(n, dtype=torch.int64)
+        a = ((m * m) % (2 * n)).to(torch.float64) * (-torch.pi / n)
+        c = torch.complex(a.cos(), a.sin())
+        wrapped = torch.zeros(CZT_M, dtype=torch.complex128)
+        wrapped[:n] = c.conj()
+        wrapped[CZT_M - n + 1:] = c.conj()[1:].flip(0)
+        k = torch.arange(CZT_M)
+        order = (k // 16) + 16 * (k % 16)                 # entry 16 k1 + k2 <- element k1 + 16 k2
+        bf = torch.fft.fft(wrapped)[order] / CZT_M
+        bi = torch.fft.fft(wrapped.conj())[order] / CZT_M
+        w = torch.arange(CZT_M, dtype=torch.float64) * (-2.0 * torch.pi / CZT_M)
+        cpad = torch.zeros(CZT_MAX, dtype=torch.complex128)
+        cpad[:n] = c
+        table = torch.cat([cpad, bf, bi, torch.complex(w.cos(), w.sin())])
+        return torch.view_as_real(table).float().contiguous().to(device)
+    return memo("lfm_tw_czt", n, device, make)
+
+
 def _route(h, w):
     """0: csrc/lfm_dft.hip serves the map; 1: csrc/lfm_dft_any.hip does; raises when neither."""
     if dft_supported(h, w):
@@ -324,14 +359,36 @@ def _pair_cl(y):
     return v if v.is_contiguous() else v.contiguous()
 
 
-def _spectrum(x_nhwc, coef, high, norm, dtype):
+def _czt_args(h, w, czt, dev):
+    """What the _czt entries get after the arguments of the _any entries' tables: (tw_h, tw_w, plans..., cz_h, cz_w).  A chirp axis has the
+    plan (1, 1, L) and its chirp table (also handed over as its tw, which is not read); the other axis its _any table and _axis_plan."""
+    tw, plans, cz = [], [], []
+    for length, on in ((h, czt[0]), (w, czt[1])):
+        if on:
+            if not CZT_MIN <= length <= CZT_MAX:
+                raise RuntimeError(f"LFM transforms: a chirp axis of length {length} is outside {CZT_MIN}..{CZT_MAX}")
+            t = _twiddles_czt(length, dev)
+            tw.append(t.data_ptr()), plans.extend((1, 1, length)), cz.append(t.data_ptr())
+        else:
+            if dft_plan(length) is None:
+                raise RuntimeError(f"LFM transforms: an axis of length {length} beside a chirp axis is not served by csrc/lfm_dft_any.hip")
+            tw.append(_twiddles_any(length, dev).data_ptr()), plans.extend(_axis_plan(length)), cz.append(None)
+    return tw, plans, cz
+
+
+def _spectrum(x_nhwc, coef, high, norm, dtype, czt=(False, False)):
     n, h, w, c = x_nhwc.shape
     dev = x_nhwc.device
-    any_ = _route(h, w)
+    czt = (bool(czt[0]), bool(czt[1]))
+    any_ = 2 if any(czt) else _route(h, w)
     tmp = torch.empty((n, h, w // 2 + 1, c, 2), dtype=torch.float32, device=dev)
     pair = torch.empty((n, h, w, 2 * c), dtype=dtype, device=dev)
     args = (x_nhwc.data_ptr(), coef.data_ptr() if coef is not None else None, high.data_ptr() if high is not None else None, n, h, w, c)
-    if any_:
+    if any_ == 2:
+        tw, plans, cz = _czt_args(h, w, czt, dev)
+        check(lib().ocpg_lfm_spectrum_fwd_czt(*args, *tw, float(norm), tmp.data_ptr(), pair.data_ptr(), _DT[dtype], *plans, *cz,
+                                              torch.cuda.current_stream().cuda_stream), "ocpg_lfm_spectrum_fwd_czt")
+    elif any_:
         check(lib().ocpg_lfm_spectrum_fwd_any(*args, _twiddles_any(h, dev).data_ptr(), _twiddles_any(w, dev).data_ptr(), float(norm), tmp.data_ptr(),
                                               pair.data_ptr(), _DT[dtype], *_axis_plan(h), *_axis_plan(w), torch.cuda.current_stream().cuda_stream),
               "ocpg_lfm_spectrum_fwd_any")
@@ -341,19 +398,23 @@ def _spectrum(x_nhwc, coef, high, norm, dtype):
     return pair
 
 
-def _inverse(pair, coef, high, z_saved, want_coef, norm, residual):
+def _inverse(pair, coef, high, z_saved, want_coef, norm, residual, czt=(False, False)):
     n, h, w, c2 = pair.shape
     c = c2 // 2
     dev = pair.device
-    any_ = _route(h, w)
-    slab = _slab(h) if any_ else 64
+    czt = (bool(czt[0]), bool(czt[1]))
+    any_ = 2 if any(czt) else _route(h, w)
+    slab = CZT_SLAB if czt[0] else _slab(h) if any_ else 64
     tmp = torch.empty((n, h, w // 2 + 1, c, 2), dtype=torch.float32, device=dev)
     out = torch.empty((n, h, w, c), dtype=torch.float32, device=dev)
     part = torch.empty((n, (w // 2 + 1) * ((c + slab - 1) // slab)), dtype=torch.float32, device=dev) if want_coef else None
     args = (pair.data_ptr(), _DT[pair.dtype], coef.data_ptr() if coef is not None else None, high.data_ptr() if high is not None else None,
             z_saved.data_ptr() if want_coef else None, part.data_ptr() if want_coef else None, n, h, w, c)
     tail = (float(norm), tmp.data_ptr(), residual.data_ptr() if residual is not None else None, out.data_ptr())
-    if any_:
+    if any_ == 2:
+        tw, plans, cz = _czt_args(h, w, czt, dev)
+        check(lib().ocpg_lfm_spectrum_inv_czt(*args, *tw, *tail, *plans, *cz, torch.cuda.current_stream().cuda_stream), "ocpg_lfm_spectrum_inv_czt")
+    elif any_:
         check(lib().ocpg_lfm_spectrum_inv_any(*args, _twiddles_any(h, dev).data_ptr(), _twiddles_any(w, dev).data_ptr(), *tail, *_axis_plan(h),
                                               *_axis_plan(w), torch.cuda.current_stream().cuda_stream), "ocpg_lfm_spectrum_inv_any")
     else:
@@ -368,11 +429,12 @@ class LFMSpectrum(Function):
     inverse transform of gate * gz, and the gate coefficient's gradient from the saved z."""
 
     @staticmethod
-    def forward(ctx, x, coef, high, dtype):
+    def forward(ctx, x, coef, high, dtype, czt=(False, False)):
         xs = _nhwc32(x)
         coef, high = coef.float().contiguous(), high.float().contiguous()
-        pair = _spectrum(xs, coef, high, 1.0, dtype)
+        pair = _spectrum(xs, coef, high, 1.0, dtype, czt)
         ctx.save_for_backward(pair, coef, high)
+        ctx.czt = czt
         return pair.permute(0, 3, 1, 2)
 
     @staticmethod
@@ -383,8 +445,8 @@ class LFMSpectrum(Function):
         if g.dtype != pair.dtype:
             g = g.to(pair.dtype)
         want_coef = ctx.needs_input_grad[1]
-        gx, part = _inverse(g, coef, high, pair, want_coef, 1.0, None)
-        return gx.permute(0, 3, 1, 2), (part.sum(1) if want_coef else None), None, None
+        gx, part = _inverse(g, coef, high, pair, want_coef, 1.0, None, ctx.czt)
+        return gx.permute(0, 3, 1, 2), (part.sum(1) if want_coef else None), None, None, None
 
 
 class LFMInverse(Function):
@@ -392,11 +454,12 @@ class LFMInverse(Function):
     csrc/lfm_dft.hip; fp32 result in channels-last memory.  Backward: fft2(g) / (h w) as a [Re || Im] pair in y's dtype; g for x."""
 
     @staticmethod
-    def forward(ctx, y, x):
+    def forward(ctx, y, x, czt=(False, False)):
         ys, xs = _pair_cl(y), _nhwc32(x)
         n, h, w, _ = ys.shape
-        out, _ = _inverse(ys, None, None, None, False, 1.0 / (h * w), xs)
+        out, _ = _inverse(ys, None, None, None, False, 1.0 / (h * w), xs, czt)
         ctx.dtype = (y.dtype, ys.dtype)
+        ctx.czt = czt
         return out.permute(0, 3, 1, 2)
 
     @staticmethod
@@ -407,15 +470,16 @@ class LFMInverse(Function):
         if ctx.needs_input_grad[0]:
             gs = _nhwc32(g)
             n, h, w, _ = gs.shape
-            gy = _spectrum(gs, None, None, 1.0 / (h * w), sdt).permute(0, 3, 1, 2)
+            gy = _spectrum(gs, None, None, 1.0 / (h * w), sdt, ctx.czt).permute(0, 3, 1, 2)
             if gy.dtype != ydt:
                 gy = gy.to(ydt)
-        return gy, (g if ctx.needs_input_grad[1] else None)
+        return gy, (g if ctx.needs_input_grad[1] else None), None
 
 
-def lfm_spectrum(x, coef, high, dtype):
-    return LFMSpectrum.apply(x, coef, high, dtype)
+def lfm_spectrum(x, coef, high, dtype, czt=(False, False)):
+    """czt = (h, w): the axes that run the chirp-z line transform of csrc/lfm_dft_czt.hip (a length 65..128 each); the backward pass follows."""
+    return LFMSpectrum.apply(x, coef, high, dtype, (bool(czt[0]), bool(czt[1])))
 
 
-def lfm_inverse(y, x):
-    return LFMInverse.apply(y, x)
+def lfm_inverse(y, x, czt=(False, False)):
+    return LFMInverse.apply(y, x, (bool(czt[0]), bool(czt[1])))

@@ -154,6 +154,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("lfm_dft_any_ab: needs a GPU (a timing taken anywhere else says nothing)")
     dev = torch.device("cuda:0")
+    modules.DFT_CZT = False           # this tool measures the plan stages and the direct stage; the chirp axis has tools/lfm_dft_czt_ab.py
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         def emit(d):
