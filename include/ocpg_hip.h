@@ -1114,6 +1114,32 @@ int ocpg_mask_rle_encode(int n_masks, long long max_n, const int* n_trans_host, 
                          const long long* run_start, long long counts_cap, int* counts, int* n_runs, unsigned char* bytes,
                          long long* n_bytes, void* workspace, void* stream);
 
+/* Run-length deflate of 8-bit planes on the device (csrc/png_rle.hip): the deflate stream of a PNG's IDAT
+ * chunk for masks and label maps, byte for byte what models/ops/functions/png_func.py composes on the host.
+ *   Stream        filter type 0: the filtered data of an H x W plane is H rows of 0x00 + the row's W bytes.  Per row: a fixed-Huffman
+ *                 block (BFINAL = 0; the row's tokens; end-of-block) and an empty stored block, so every row ends byte-aligned.  The
+ *                 tokens of a row: its W + 1 filtered bytes cut into maximal runs of equal bytes; a run of value v and length n is
+ *                 the literal v, (n - 1) / 258 matches of length 258 at distance 1, then one match of length (n - 1) % 258 at
+ *                 distance 1 when that is >= 3, that many literals v otherwise.  Behind the last row the final block 03 00.
+ *   Two steps, so the call is NOT capturable: the length of a stream depends on the data.
+ * ocpg_png_rle_count (2 launches): planes [N, H, W] uint8, contiguous, device, no alignment needed.  Writes the row tables into
+ *   workspace (device memory, 8-byte aligned, 24 * N * H bytes) and totals [N, 3] int64 (device, 8-byte aligned): the bytes of plane
+ *   m's stream, S0 = sum(d_i) and S1 = sum(i * d_i) over its filtered data d_0 .. d_(n-1), n = H (W + 1), exact in 64 bits.
+ *   Adler-32 of the filtered data is ((n + n S0 - S1) mod 65521) << 16 | (1 + S0) mod 65521, to be finished by the caller.
+ * ocpg_png_rle_emit (1 launch): the same planes, N, H, W and workspace; totals_host = what step 1 wrote, read back (HOST memory).
+ *   The streams are written back to back into out (device, out_cap bytes, no alignment needed): plane m's at the sum of the byte
+ *   counts before it.  Bytes of out outside the streams are not written; the kernels read no word of the workspace that they did
+ *   not write in this call, clamp what they read of it, and store a row only where it lies inside out_cap.
+ * One wave per row, LDS atomic OR into a per-wave bit buffer, plain vector stores, no global atomics, no memset, no workgroup waits
+ * for another.
+ * Return codes, all before any launch (nothing written): N, H or W <= 0: -1006;  W > 4096 (the per-wave bit buffer): -2701;  N or H
+ * > 65535, or N * H > 2^22 rows (grid and the 64-bit bound of S1): -2702;  planes NULL: -1001;  workspace NULL or not 8-byte
+ * aligned: -2703;  totals NULL or not 8-byte aligned: -2704;  totals_host NULL or a byte count outside 0 .. H * (9 (W + 1) / 8 + 9):
+ * -2705;  out NULL, out_cap <= 0 or smaller than the sum of the byte counts: -2706. */
+int ocpg_png_rle_count(const unsigned char* planes, int N, int H, int W, void* workspace, long long* totals, void* stream);
+int ocpg_png_rle_emit(const unsigned char* planes, int N, int H, int W, void* workspace, const long long* totals_host,
+                      unsigned char* out, long long out_cap, void* stream);
+
 /* library / build identification: returns e.g. "ocpg_hip gfx950 r1" */
 const char* ocpg_hip_version(void);
 
